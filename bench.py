@@ -21,15 +21,19 @@ on its own stream, overlapping the extraction of batch k+1; outputs are
 triple-buffered and ordered by events (see MonoPipeline.step). --serial runs
 everything on one stream.
 
-Extra legs in the same JSON line (rank 0, N = 1; skipped with --no-latency /
---no-host-stream):
+A plain run sets up, warms up, times --steps steps, writes the last step's
+outputs if --dump-outputs DIR is given, and prints the line. Extra legs in the
+same JSON line with --full only (rank 0, N = 1; each skipped with
+--no-latency / --no-host-stream / --cpu-sample 0):
   * "latency": the call Tracking makes per frame, orbx_extract on ONE host
     1241x376 image (host in, host keypoints + descriptors out; pinned
     staging, captured hipGraph) and the host SearchForInitialization call,
     median / p99 over 200 calls, beside the oracle's single-thread latency;
   * "host_stream": the same C3 pipeline fed from pinned host memory every
     step (H2D of each batch on a copy stream, keypoints / descriptors /
-    matches copied back), PCIe-inclusive frames/s.
+    matches copied back), PCIe-inclusive frames/s;
+  * "cpu_baseline", "cpu_baseline_1thread", "tie_rule_disagreement": the CPU
+    oracle on a sample of the same frames.
 
 Multi-GPU: one process per GPU. `--gpus N` without a torchrun environment
 spawns N worker processes (multiprocessing "spawn", before this process
@@ -205,7 +209,21 @@ def parse_args(argv=None):
                     help="run even with diagnostic ORBX_* variables set (phase clocks, library variants); "
                          "the line then carries them and is not a valid measurement")
     ap.add_argument("--stub-worker", action="store_true", help=argparse.SUPPRESS)  # launcher tests (CPU)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: the single-frame and shim latency legs, the "
+                         "host-streamed leg, the CPU baselines and the CPU tie-rule study (each still subject to its "
+                         "own --no-* / --cpu-sample switch). Without it the run sets up, warms up, times --steps "
+                         "steps and prints the line with those fields null")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed pipeline computed in its last step as "
+                         "DIR/<name>.npy (float32, at most 64 MB): keypoints, descriptors, counts and matches of the "
+                         "step's last two batches (stereo: of the last step's pairs); padding beyond a frame's count "
+                         "is 0 (matches: -1), descriptors beyond the budget are a seeded sample of frames. The BoW "
+                         "stages' outputs are not written")
     a = ap.parse_args(argv)
+    if not a.full:
+        a.no_latency = a.no_shim_latency = a.no_host_stream = True
+        a.cpu_sample = 0
     if a.match_order is None:
         a.match_order = "bow,init,top2" if (a.bow or a.bow_match) else "init,top2,bow"
     return a
@@ -774,6 +792,8 @@ def run_mono(args, cfg, rank, world, local, dist):
     pipe.check_status()
     if args.dump_pairs:
         dump_batch0(args, pipe, rank, block if args.split_sequence else None, prev if args.split_sequence else None)
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, rank, world, mono_outputs(args, pipe, SUB, world))
     BS, S, cap = pipe.BS, pipe.S, pipe.cap
     timed = pipe.evsets[args.warmup * SUB:]
     ev_ms = timed[0][0].elapsed_ms(timed[-1][8])
@@ -953,6 +973,103 @@ def dump_batch0(args, pipe, rank, block, prev):
              sd=pipe.d_sd[0].download((B, cap), np.int32),
              block=np.array([block.start, block.stop] if block is not None else [-1, -1]),
              prev=np.array([-1 if prev is None else prev]))
+
+
+DUMP_BUDGET = 64 * 10 ** 6  # bytes of array data --dump-outputs writes at most (all ranks together)
+
+
+def _as_float(a):
+    """float32 where every value is exact in it, float64 otherwise (integers past 2^24)."""
+    if a.dtype.kind in "iu" and a.size and np.abs(a.astype(np.int64)).max() >= 1 << 24:
+        return a.astype(np.float64)
+    return a.astype(np.float32)
+
+
+def _kps_float(k):
+    """orbx_kp records as (..., 7) float32: x, y, size, angle, response, octave, class_id."""
+    return np.stack([k[f].astype(np.float32) for f in k.dtype.names], -1)
+
+
+def _pad(a, counts, fill):
+    """a[i, counts[i]:] = fill: entries past a frame's count are never written by the kernels."""
+    a = a.copy()
+    a[np.arange(a.shape[1])[None, :] >= np.asarray(counts)[:, None]] = fill
+    return a
+
+
+def _sampled_descriptors(out, tag, d_desc, rows_all, cap, counts, left, most, rng):
+    """Descriptors of `tag` as (rows, cap, 32) float32 plus the rows' indices: every
+    row if `left` bytes (and `most` rows) allow, else a seeded sample. Returns the bytes used."""
+    per = cap * DS * 4 + 4
+    n = int(min(rows_all, most, max(0, left // per)))
+    if n == 0:
+        return 0
+    rows = np.arange(rows_all) if n == rows_all else np.sort(rng.choice(rows_all, n, replace=False))
+    d = d_desc.download((rows_all, cap, DS), np.uint8)[rows]
+    out[f"{tag}descriptors"] = _pad(d.astype(np.float32), counts[rows], 0)
+    out[f"{tag}descriptor_frames"] = rows.astype(np.float32)
+    return n * per
+
+
+def mono_outputs(args, pipe, sub, world=1):
+    """--dump-outputs: what the last timed step left in the pipeline's output sets,
+    as a caller reading them after the step would find it. A step is `sub`
+    batches over three output sets, and a batch's slot 0 (frame t-1 of its first
+    frame) is rewritten two batches later, so the step's last two batches are
+    whole: batch<i>_* for i counted within the step. Per batch: counts (B + 1;
+    row 0 is frame t-1, rows 1..B the batch's frames), keypoints (B + 1, cap, 7),
+    descriptors (rows, cap, 32) of the frames listed in descriptor_frames, and
+    per pair p (frame row p -> row p + 1) SearchForInitialization's matches12
+    (over row p's keypoints) and the dense top-2 (over row p + 1's)."""
+    import orb_slam_cuda_amd as pkg
+    B, cap, NS = pipe.B, pipe.cap, pipe.NS
+    keep = min(sub, 2, pipe.total)
+    out, sets = {}, []
+    for j in range(keep):
+        k = pipe.total - keep + j
+        b, tag = k % NS, f"batch{sub - keep + j}_"
+        cnt = np.clip(pipe.d_counts[b].download(B + 1, np.int32), 0, cap)
+        sets.append((tag, b, cnt))
+        out[tag + "counts"] = _as_float(cnt)
+        out[tag + "keypoints"] = _pad(_kps_float(pipe.d_kps[b].download((B + 1, cap), pkg.KP_DTYPE)), cnt, 0)
+        if not args.no_match:
+            for name, d, n in (("init_matches12", pipe.d_m12, cnt[:-1]), ("top2_best_index", pipe.d_bi, cnt[1:]),
+                               ("top2_best_distance", pipe.d_bd, cnt[1:]),
+                               ("top2_second_distance", pipe.d_sd, cnt[1:])):
+                out[tag + name] = _as_float(_pad(d[b].download((B, cap), np.int32), n, -1))
+            out[tag + "init_nmatches"] = _as_float(pipe.d_nm[b].download(B, np.int32))
+    left = DUMP_BUDGET // world - sum(a.nbytes for a in out.values())
+    rng = np.random.default_rng(0)
+    for j, (tag, b, cnt) in enumerate(reversed(sets)):  # the last batch first: whole if it fits
+        left -= _sampled_descriptors(out, tag, pipe.d_desc[b], B + 1, cap, cnt, left, B + 1 if j == 0 else 16, rng)
+    return out
+
+
+def stereo_outputs(st, B, cap, world=1):
+    """--dump-outputs of the stereo config: the last step's handle set. counts (2B:
+    the B left images, then the B right ones), keypoints (2B, cap, 7), descriptors
+    of the images listed in descriptor_frames, and per pair ComputeStereoMatches'
+    uright and depth (B, cap; over the left image's keypoints) and kept."""
+    import orb_slam_cuda_amd as pkg
+    n = np.clip(st["n"].download(2 * B, np.int32), 0, cap)
+    out = {"counts": _as_float(n),
+           "keypoints": _pad(_kps_float(st["kps"].download((2 * B, cap), pkg.KP_DTYPE)), n, 0),
+           "uright": _pad(st["u"].download((B, cap), np.float32), n[:B], -1),
+           "depth": _pad(st["d"].download((B, cap), np.float32), n[:B], -1),
+           "kept": _as_float(st["kept"].download(B, np.int32))}
+    left = DUMP_BUDGET // world - sum(a.nbytes for a in out.values())
+    _sampled_descriptors(out, "", st["desc"], 2 * B, cap, n, left, 2 * B, np.random.default_rng(0))
+    return out
+
+
+def write_outputs(dirname, rank, world, arrays):
+    """DIR/<name>.npy (rank<r>_<name>.npy when several ranks run), float32 / float64 only."""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET // world or any(a.dtype not in (np.float32, np.float64) for a in arrays.values()):
+        raise RuntimeError(f"--dump-outputs: {total} bytes / dtypes {sorted({str(a.dtype) for a in arrays.values()})}")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, (f"rank{rank}_" if world > 1 else "") + name + ".npy"), a)
 
 
 SQ_LAUNCH_FRAMES = 32   # frames per extraction launch of the committed SQ counter run
@@ -1412,6 +1529,8 @@ def run_stereo(args, cfg, rank, world, local, dist):
         sm["stereo"] += ev[6].elapsed_ms(ev[7])
     sm = {s: v / args.steps for s, v in sm.items()}
     last = sets[(total - 1) % NSET]
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, rank, world, stereo_outputs(last, B, cap, world))
     kept = last["kept"].download(B, np.int32)
     nkp = last["n"].download(2 * B, np.int32)
     ab = algorithmic_bytes(W, H, float(nkp.mean()))

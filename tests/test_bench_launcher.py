@@ -88,6 +88,36 @@ def test_parse_defaults():
     assert bench.parse_args(["--bow-match"]).match_order == "bow,init,top2"
 
 
+def test_plain_run_has_no_extra_legs():
+    """Without --full every leg beside the timed steps is off; with it each keeps its own switch."""
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert not a.full and a.steps == 7 and a.dump_outputs is None
+    assert a.no_latency and a.no_shim_latency and a.no_host_stream and a.cpu_sample == 0
+    f = bench.parse_args(["--full"])
+    assert not (f.no_latency or f.no_shim_latency or f.no_host_stream) and f.cpu_sample == 200
+    assert bench.parse_args(["--full", "--no-latency", "--cpu-sample", "0"]).no_latency
+
+
+def test_dump_outputs_arrays_are_float_and_bounded(tmp_path):
+    """write_outputs takes float32 / float64 within the budget only; padding and
+    the integer conversion keep every value exact."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    small, big = np.array([[1, 2, 3], [4, 5, 6]], np.int32), np.array([2 ** 31 - 1, -1], np.int32)
+    assert bench._as_float(small).dtype == np.float32 and bench._as_float(big).dtype == np.float64
+    assert bench._as_float(big).astype(np.int64).tolist() == big.tolist()
+    assert bench._pad(small, [1, 3], -1).tolist() == [[1, -1, -1], [4, 5, 6]]
+    bench.write_outputs(str(tmp_path / "d"), 0, 1, {"x": bench._as_float(small)})
+    assert np.array_equal(np.load(tmp_path / "d" / "x.npy"), small)
+    with pytest.raises(RuntimeError):
+        bench.write_outputs(str(tmp_path / "d"), 0, 1, {"x": small})
+    with pytest.raises(RuntimeError):
+        bench.write_outputs(str(tmp_path / "d"), 0, 1, {"x": np.zeros(bench.DUMP_BUDGET // 4 + 1, np.float32)})
+
+
 @pytest.mark.parametrize("order,ok", [("init,top2,bow", True), ("bow,top2,init", True), ("top2,bow", False),
                                       ("top2,top2,init", False), ("top2,bow,init,x", False)])
 def test_parse_match_order(order, ok):

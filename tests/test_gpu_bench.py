@@ -25,8 +25,8 @@ def _bench(args, timeout=240):
 
 
 def test_bench_launcher_one_gpu():
-    out = _bench(["--gpus", "1", "--spawn", "--steps", "3", "--warmup", "1", "--pool", "128", "--cpu-sample", "0",
-                  "--host-steps", "3"])
+    out = _bench(["--gpus", "1", "--spawn", "--full", "--steps", "3", "--warmup", "1", "--pool", "128",
+                  "--cpu-sample", "0", "--host-steps", "3"])
     assert out["n_gpus"] == 1 and len(out["per_rank_frames_per_s"]) == 1
     assert out["value"] > 0 and out["unit"] == "frames/s"
     assert out["roofline"]["frac"] > 0 and out["roofline"]["bound"] == "hbm"
@@ -37,6 +37,51 @@ def test_bench_launcher_one_gpu():
     assert out["host_stream"]["value"] > 0
     tie = out["quadtree_tie_straddle"]
     assert tie["frames"] == 64 and 0 <= tie["fraction_of_kept"] < 0.5
+
+
+def test_bench_plain_run_dumps_last_step(O, tmp_path):
+    """A plain run (no --full) carries the headline figures only, and
+    --dump-outputs writes the last timed step's last two batches as float
+    arrays within 64 MB. With --pool 64 every batch holds frames 0..63 of the
+    rank-0 sequence (row 0: frame 63, carried from the batch before), so rows
+    5 and 6 are frames 4 and 5: keypoints, descriptors, dense top-2 and
+    SearchForInitialization of that pair equal the oracle's."""
+    import numpy as np
+    from oracle.oracle import KP_DTYPE
+    from orb_slam_cuda_amd.synth import SynthSequence
+    out = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--pool", "64", "--dump-outputs", str(tmp_path)])
+    for leg in ("latency", "shim_latency", "shim_matcher_latency", "host_stream", "cpu_baseline",
+                "cpu_baseline_1thread", "tie_rule_disagreement"):
+        assert out[leg] is None, leg
+    assert out["steps"] == 2 and out["unit"] == "frames/s" and out["dtype"] == "u8" and out["higher_is_better"]
+    assert out["ms_per_step"] > 0 and abs(out["value"] - 4 * 64 * 1e3 / out["ms_per_step"]) < 1e-3 * out["value"]
+    arrays = {f.stem: np.load(f) for f in tmp_path.glob("*.npy")}
+    assert sum(a.nbytes for a in arrays.values()) <= 64e6
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    W, H = 1241, 376
+    fr = SynthSequence(1000, W, H).frames(6)
+    cfg = O.config(nfeatures=2000, width=W, height=H)
+    (k1, d1), (k2, d2) = O.extract(cfg, fr[4]), O.extract(cfg, fr[5])
+    ri, rd, rs = O.hamming_top2(d2, d1)
+    r12, rnm, _ = O.search_for_initialization(k1, d1, k2, d2, (0, W, 0, H), np.stack([k1["x"], k1["y"]], 1),
+                                              100, 0.9, True)
+    ref_kp = lambda k: np.stack([k[f].astype(np.float32) for f in KP_DTYPE.names], -1)
+    for tag in ("batch2_", "batch3_"):  # the last two of the step's four batches
+        a = {n[len(tag):]: v for n, v in arrays.items() if n.startswith(tag)}
+        cnt = a["counts"].astype(int)
+        assert cnt.shape == (65,) and cnt[5] == len(k1) and cnt[6] == len(k2)
+        kp = a["keypoints"]
+        assert np.array_equal(kp[5, :cnt[5]], ref_kp(k1)) and np.array_equal(kp[6, :cnt[6]], ref_kp(k2))
+        assert not kp[5, cnt[5]:].any()  # padding past the count
+        rows = a["descriptor_frames"].astype(int).tolist()
+        assert a["descriptors"].shape[0] == len(rows) >= 16
+        if 6 in rows:
+            assert np.array_equal(a["descriptors"][rows.index(6), :cnt[6]], d2)
+        for name, want in (("top2_best_index", ri), ("top2_best_distance", rd), ("top2_second_distance", rs)):
+            assert np.array_equal(a[name][5, :cnt[6]], want), name
+        assert a["init_nmatches"][5] == rnm > 20 and np.array_equal(a["init_matches12"][5, :cnt[5]], r12)
+        assert (a["init_matches12"][5, cnt[5]:] == -1).all()
+    assert arrays["batch3_descriptor_frames"].tolist() == list(range(65))  # the last batch whole
 
 
 def test_bench_euroc_and_extract_only():

@@ -10,7 +10,7 @@ mkdir -p $OUT
 cd /tmp; export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
 run() {  # name, bench args
   local name=$1; shift
-  timeout -k 10 300 python3 bench.py --cpu-sample 0 "$@" > $OUT/$name.log 2>&1
+  timeout -k 10 300 python3 bench.py --full --cpu-sample 0 "$@" > $OUT/$name.log 2>&1
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$name -o run -- \
     python3 bench.py --cpu-sample 0 --no-latency --no-host-stream --steps 30 --warmup 5 "$@" > $OUT/${name}_prof.log 2>&1
   echo "$name done"

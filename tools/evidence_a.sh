@@ -11,7 +11,7 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -v --timeout 240 --timeout-me
 tail -n 1 $O/gpu_tests.log
 timeout -k 10 120 python3 -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
 cat $O/smoke.log
-timeout -k 10 400 python3 bench.py > $O/bench_default.log 2>&1
+timeout -k 10 400 python3 bench.py --full > $O/bench_default.log 2>&1
 tail -n 1 $O/bench_default.log | cut -c1-300
 bash tools/profile_round.sh $R --steps 30 --warmup 5 > $O/prof_main.txt 2>&1
 cd /tmp; export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"

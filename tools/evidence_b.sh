@@ -39,6 +39,6 @@ timeout -k 10 120 python3 tools/h2d_bench.py > $O/h2d.json
 # sq_valu.json from the passes above)
 cp $O/sq_valu.json profiles/sq_valu.json
 mkdir -p gpurun_out/ev_${R}c
-timeout -k 10 400 python3 bench.py > gpurun_out/ev_${R}c/bench_default.log 2>&1
+timeout -k 10 400 python3 bench.py --full > ${O%b}c/bench_default.log 2>&1
 tail -n 1 gpurun_out/ev_${R}c/bench_default.log | cut -c1-200
 echo all-done
