@@ -985,14 +985,15 @@ int orbx_frame_capacity(orbx_handle h) { return h ? h->plan.P.kp_per_frame : 0; 
 int orbx_extract_batch(orbx_handle h, const uint8_t* d_frames, int batch, size_t frame_pitch, size_t row_stride,
                        orbx_kp* d_kps, uint8_t* d_desc, int* d_counts, void* stream) {
   if (!h || !d_frames || !d_kps || !d_desc || !d_counts) return fail(ORBX_EINVAL, "null argument");
+  // one call of a handle at a time: a synchronous orbx_extract in flight on
+  // another thread holds the lock until its chain has finished (it records
+  // no workspace event for a batch call to wait on), and it may re-plan the
+  // handle for a new image size, so the plan is checked under the lock
+  std::lock_guard<std::mutex> lk(h->mu);
   if (batch < 1 || batch > h->plan.B) return fail(ORBX_EINVAL, "batch %d not in 1..max_batch(%d)", batch, h->plan.B);
   if (h->plan.W == 0)
     return fail(ORBX_EINVAL, "no frame size yet: the handle was created with width/height 0 and has seen no orbx_extract");
   if (row_stride < (size_t)h->plan.W) return fail(ORBX_EINVAL, "row_stride < width");
-  // one call of a handle at a time: a synchronous orbx_extract in flight on
-  // another thread holds the lock until its chain has finished (it records
-  // no workspace event for a batch call to wait on)
-  std::lock_guard<std::mutex> lk(h->mu);
   HIP_OK(hipSetDevice(h->cfg.device));
   void** ev = h->has_user_ev ? h->user_ev : (h->timing ? (void**)h->ev : nullptr);
   h->has_user_ev = false;
@@ -1470,8 +1471,8 @@ int orbx_get_stage_times(orbx_handle h, float* ms, const char** names, int cap, 
       default: return "Compute angle+ORB descriptor+scale";
     }
   };
-  const char* order = h->order;
   if (!h || !n) return fail(ORBX_EINVAL, "null argument");
+  const char* order = h->order;
   *n = 0;
   if (!h->timing) return ORBX_OK;
   HIP_OK(hipEventSynchronize(h->ev[5]));

@@ -224,11 +224,28 @@ int launch_extract(const ExtractParams& P, const ExtractBuffers& X, const uint8_
                    uint8_t* d_desc, int* d_counts, void* stream, void** stage_events,
                    void* pyr_event = nullptr, int* status_dst = nullptr, const char* stage_order = nullptr);
 
-// orbx_match.hip
+// orbx_top2.hip — dense Hamming best/second search
 int launch_hamming_top2(const uint8_t* A, size_t a_pitch, const int* nA, int a_cap,
                         const uint8_t* B, size_t b_pitch, const int* nB, int pairs, int* best_idx,
                         int* best, int* second, int* err, void* stream);
-
+// orbx_bow.hip — SearchByBoW over a batch of pairs; one side of the pairs:
+struct BowSide {
+  const uint8_t* desc;  // pair p: desc + p * kp_pitch * 32
+  const float* angle;   // keypoint i's angle at angle[p * kp_pitch * angle_stride + i * angle_stride]
+  int angle_stride;     // 1 for an angle array, 7 for orbx_kp records
+  const uint8_t* mp;    // has a (good) MapPoint, or null = all
+  const int* n;         // features per pair
+  const uint32_t* nodes;  // FeatureVector CSR: pair p at p * node_pitch (off: p * (node_pitch + 1))
+  const int* off;
+  const int* idx;
+  const int* nn;        // nodes per pair
+  long long kp_pitch, node_pitch;
+};
+int launch_search_bow(const BowSide& A, const BowSide& B, int pairs, float nnratio, int check_ori, int kf_vs_kf,
+                      int* out, long long out_pitch, int* nmatches, int* rec_scratch, size_t rec_ints,
+                      int* hist_scratch, size_t hist_ints, bool* clean, int* err, void* stream);
+// the Frame / KeyFrame keypoint grid (FRAME_GRID_COLS / ROWS include/Frame.h:37-38)
+constexpr int kGridCols = 64, kGridRows = 48;
 
 // orbx_stereo.hip — Frame::ComputeStereoMatches over a batch of rectified pairs.
 // Pyramid pointers address pair 0; pair p's level l is at base[l] + p * fstride[l].

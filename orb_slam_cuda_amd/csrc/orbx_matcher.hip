@@ -1,0 +1,1229 @@
+// orbx_matcher.hip — the orbm_* C ABI: the matcher handle, the stream order of
+// its workspaces, the batch (device-array) entry points and the synchronous
+// host-array entry points staged through the handle's arena. The kernels are in
+// orbx_top2.hip, orbx_bow.hip, orbx_init.hip, orbx_stereo.hip,
+// orbx_project.hip, orbx_project_pose.hip and orbx_triangulate.hip.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <climits>
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "orbx_internal.h"
+
+using namespace orbx;
+
+namespace {
+thread_local std::string g_merr;
+int mfail(int code, const char* fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  g_merr = buf;
+  return code;
+}
+}  // namespace
+
+extern "C" const char* orbm_last_error(void) { return g_merr.c_str(); }
+
+#define MHIP(expr)                                                                             \
+  do {                                                                                         \
+    hipError_t e_ = (expr);                                                                    \
+    if (e_ != hipSuccess) return mfail(ORBX_EDEVICE, "%s: %s", #expr, hipGetErrorString(e_));  \
+  } while (0)
+
+struct orbx_matcher {
+  int device = 0, max_pairs = 0, max_kps = 0;
+  int sortn = 1;
+  int* init_ws = nullptr;  // SearchForInitialization: per-pair records, keys (init_ws_bytes_per_pair)
+  size_t init_ws_pair = 0;  // bytes per pair
+  int* host_init_ws = nullptr;  // orbm_search_for_initialization's own (its pitch is the call's)
+  size_t host_init_ws_bytes = 0;
+  int* err = nullptr;
+  int* stereo_sad = nullptr;  // [max_pairs][max_kps] SAD per left keypoint (-1 = none)
+  int* bow_hist = nullptr;    // [max_pairs][32] SearchByBoW rotation histogram (+ match count), 0 between calls
+  int* bow_rec = nullptr;     // [max_pairs][max_kps] SearchByBoW row records, -1 between calls
+  bool bow_clean = false;     // bow_hist / bow_rec hold their between-calls values
+  int* pose_picks = nullptr;  // pose-projection picks per point (frames x mp_pitch)
+  size_t pose_picks_cap = 0;
+  hipStream_t stream = nullptr;
+  WsOrder ws;  // stream order of cand / stereo_sad / pose_picks / bow_* across caller streams
+  StreamMarks errm;  // streams of the launches that may set `err` (top-2, SearchByBoW)
+  // staging for the synchronous entry points
+  void* stage = nullptr;
+  size_t stage_bytes = 0;
+  void* h_stage = nullptr;  // pinned host staging (orbm_compute_stereo_matches_last)
+  size_t h_stage_bytes = 0;
+};
+
+static int stage_reserve(orbx_matcher* m, size_t bytes) {
+  if (m->stage_bytes >= bytes) return ORBX_OK;
+  if (m->stage) (void)hipFree(m->stage);
+  m->stage = nullptr;
+  m->stage_bytes = 0;
+  MHIP(hipMalloc(&m->stage, bytes));
+  m->stage_bytes = bytes;
+  return ORBX_OK;
+}
+
+static int host_stage_reserve(orbx_matcher* m, size_t bytes) {
+  if (m->h_stage_bytes >= bytes) return ORBX_OK;
+  if (m->h_stage) (void)hipHostFree(m->h_stage);
+  m->h_stage = nullptr;
+  m->h_stage_bytes = 0;
+  MHIP(hipHostMalloc(&m->h_stage, bytes, hipHostMallocDefault));
+  m->h_stage_bytes = bytes;
+  return ORBX_OK;
+}
+
+// the handle's own stream (status polls and the synchronous entry points), created on first use
+static int matcher_stream(orbx_matcher* m, hipStream_t* st) {
+  if (!m->stream) MHIP(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
+  *st = m->stream;
+  return ORBX_OK;
+}
+
+namespace {
+// A typed range of the handle's arena: a device pointer once Stage::reserve has run.
+template <class T>
+struct Slot {
+  void* const* base;
+  size_t off;
+  operator T*() const { return (T*)((uint8_t*)*base + off); }
+};
+
+// One synchronous (host-array) call's use of the handle's arena and stream:
+// carve the slots, reserve, upload, run the batch entry on `st`, download,
+// finish (the call's one wait). Leaving the scope any other way with work
+// enqueued waits for the stream first: the next call on the handle reuses the
+// arena, and the caller's arrays must not be in use after the return.
+//
+// Every slot starts at a multiple of 256 bytes from the arena's base (a
+// hipMalloc allocation, aligned at least as much). The kernels need 16: they
+// read descriptors as uint4 pairs (orbx_init, orbx_stereo, orbx_projgrid.cuh
+// for the two projection kernels, orbx_triangulate, orbx_bow). orbx_kp records
+// (28 bytes apart) and the map point, pose and pair records are read field by
+// field, everything else is 1- and 4-byte arrays. 256 also keeps two slots
+// out of one cache line.
+struct Stage {
+  orbx_matcher* m;
+  hipStream_t st = nullptr;
+  size_t used = 0;
+  bool pending = false;  // work enqueued on st that finish() has not waited for
+  explicit Stage(orbx_matcher* m_) : m(m_) {}
+  ~Stage() {
+    if (pending) (void)hipStreamSynchronize(st);
+  }
+  template <class T>
+  Slot<T> slot(size_t count) {
+    const Slot<T> s{&m->stage, used};
+    used += (count * sizeof(T) + 255) & ~(size_t)255;
+    return s;
+  }
+  int open() { return matcher_stream(m, &st); }
+  int reserve() {
+    const int rc = stage_reserve(m, used);
+    return rc ? rc : open();
+  }
+  // one copy per call; an absent array (count 0 or src null) is skipped
+  int copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+    if (!bytes || !src) return ORBX_OK;
+    pending = true;
+    MHIP(hipMemcpyAsync(dst, src, bytes, kind, st));
+    return ORBX_OK;
+  }
+  template <class T>
+  int up(Slot<T> dst, const T* src, size_t count) {
+    return copy(dst, src, count * sizeof(T), hipMemcpyHostToDevice);
+  }
+  template <class T>
+  int down(T* dst, Slot<T> src, size_t count) {
+    return copy(dst, src, count * sizeof(T), hipMemcpyDeviceToHost);
+  }
+  int finish() {
+    pending = false;
+    MHIP(hipStreamSynchronize(st));
+    return ORBX_OK;
+  }
+};
+}  // namespace
+
+// minX .. invH of InitParams / ProjParams / PoseParams from the frame's image
+// bounds: mfGridElementWidthInv / HeightInv = FRAME_GRID_COLS / (mnMaxX - mnMinX),
+// FRAME_GRID_ROWS / (mnMaxY - mnMinY) (src/Frame.cc:154-155)
+template <class Params>
+static void set_grid_bounds(Params& P, const orbm_grid_bounds& b) {
+  P.minX = b.min_x;
+  P.maxX = b.max_x;
+  P.minY = b.min_y;
+  P.maxY = b.max_y;
+  P.invW = static_cast<float>(kGridCols) / static_cast<float>(b.max_x - b.min_x);
+  P.invH = static_cast<float>(kGridRows) / static_cast<float>(b.max_y - b.min_y);
+}
+
+static int search_init_launch(orbx_matcher* m, const orbx_kp* d_kp1, const uint8_t* d_desc1, const int* d_n1,
+                              const orbx_kp* d_kp2, const uint8_t* d_desc2, const int* d_n2, int kp_pitch, int pairs,
+                              orbm_grid_bounds b, float* d_prev_xy, int window, float nnratio, int check_ori,
+                              int* d_matches12, int* d_nmatches, void* stream, int* ws) {
+  InitParams P{};
+  set_grid_bounds(P, b);  // F2's grid
+  P.r = (float)window;
+  P.nnratio = nnratio;
+  P.check_ori = check_ori;
+  P.kp_pitch = kp_pitch;
+  if (m->ws.before((hipStream_t)stream)) return mfail(ORBX_EDEVICE, "stream wait on the workspace failed");
+  const int rc = launch_search_init(P, d_kp1, d_desc1, d_n1, d_kp2, d_desc2, d_n2, d_prev_xy, ws, d_matches12,
+                                    d_nmatches, pairs, stream);
+  if (!rc && m->ws.after((hipStream_t)stream)) return mfail(ORBX_EDEVICE, "event record failed");
+  if (rc == ORBX_ECAPACITY)
+    return mfail(ORBX_ECAPACITY, "kp_pitch %d too large for SearchForInitialization at nnratio %g (<= %d)", kp_pitch,
+                 (double)nnratio, search_init_max_pitch(nnratio));
+  if (rc) return mfail(ORBX_EDEVICE, "search_init launch: %s", hipGetErrorString(hipGetLastError()));
+  return ORBX_OK;
+}
+
+extern "C" {
+
+int orbm_create(int device, int max_pairs, int max_kps, orbm_handle* out) {
+  if (!out || max_pairs < 1 || max_kps < 1) return mfail(ORBX_EINVAL, "bad argument");
+  if (max_kps > 65535) return mfail(ORBX_EINVAL, "max_kps must be <= 65535");
+  MHIP(hipSetDevice(device));
+  orbx_matcher* m = new orbx_matcher();
+  m->device = device;
+  m->max_pairs = max_pairs;
+  m->max_kps = max_kps;
+  while (m->sortn < max_kps) m->sortn <<= 1;
+  m->init_ws_pair = init_ws_bytes_per_pair(max_kps);
+  if (hipMalloc(&m->init_ws, (size_t)max_pairs * m->init_ws_pair) != hipSuccess ||
+      hipMalloc(&m->err, 16) != hipSuccess ||
+      hipMalloc(&m->stereo_sad, (size_t)max_pairs * max_kps * 4) != hipSuccess ||
+      hipMalloc(&m->bow_hist, (size_t)max_pairs * 32 * 4) != hipSuccess ||
+      hipMalloc(&m->bow_rec, (size_t)max_pairs * max_kps * 4) != hipSuccess) {
+    orbm_destroy(m);
+    return mfail(ORBX_ENOMEM, "matcher workspace allocation failed");
+  }
+  (void)hipMemset(m->err, 0, 16);
+  *out = m;
+  return ORBX_OK;
+}
+
+int orbm_destroy(orbm_handle m) {
+  if (!m) return ORBX_OK;
+  (void)hipSetDevice(m->device);
+  if (m->stream) (void)hipStreamSynchronize(m->stream);
+  if (m->ws.ev) (void)hipEventSynchronize(m->ws.ev);
+  m->ws.release();
+  (void)m->errm.wait();
+  m->errm.release();
+  if (m->init_ws) (void)hipFree(m->init_ws);
+  if (m->host_init_ws) (void)hipFree(m->host_init_ws);
+  if (m->err) (void)hipFree(m->err);
+  if (m->stereo_sad) (void)hipFree(m->stereo_sad);
+  if (m->bow_hist) (void)hipFree(m->bow_hist);
+  if (m->bow_rec) (void)hipFree(m->bow_rec);
+  if (m->pose_picks) (void)hipFree(m->pose_picks);
+  if (m->stage) (void)hipFree(m->stage);
+  if (m->h_stage) (void)hipHostFree(m->h_stage);
+  if (m->stream) (void)hipStreamDestroy(m->stream);
+  delete m;
+  return ORBX_OK;
+}
+
+int orbm_get_status(orbm_handle m, int reset, int* status) {
+  if (!m || !status) return mfail(ORBX_EINVAL, "null argument");
+  MHIP(hipSetDevice(m->device));
+  // the kernels that set the word ran on caller streams: wait for those
+  // launches (their stream marks), not for the device
+  if (m->errm.wait()) return mfail(ORBX_EDEVICE, "status: event wait failed");
+  hipStream_t st;
+  int rc;
+  if ((rc = matcher_stream(m, &st))) return rc;
+  int e = 0;
+  MHIP(hipMemcpyAsync(&e, m->err, 4, hipMemcpyDeviceToHost, st));
+  MHIP(hipStreamSynchronize(st));
+  if (reset && e) {
+    MHIP(hipMemsetAsync(m->err, 0, 16, st));
+    MHIP(hipStreamSynchronize(st));
+  }
+  *status = e;
+  return ORBX_OK;
+}
+
+int orbm_descriptor_distance(const uint8_t* a, const uint8_t* b) {
+  int d = 0;
+  for (int i = 0; i < 32; ++i) d += __builtin_popcount((unsigned)(a[i] ^ b[i]));
+  return d;
+}
+
+int orbm_hamming_top2(orbm_handle m, const uint8_t* d_A, size_t a_pitch, const int* d_nA, int a_cap,
+                      const uint8_t* d_B, size_t b_pitch, const int* d_nB, int pairs, int* d_best_idx, int* d_best,
+                      int* d_second, void* stream) {
+  if (!m || !d_A || !d_B || !d_nA || !d_nB || pairs < 1) return mfail(ORBX_EINVAL, "bad argument");
+  if ((a_pitch | b_pitch) & 15) return mfail(ORBX_EINVAL, "pitches must be multiples of 16 bytes");
+  MHIP(hipSetDevice(m->device));
+  const int rc = launch_hamming_top2(d_A, a_pitch, d_nA, a_cap, d_B, b_pitch, d_nB, pairs, d_best_idx, d_best,
+                                     d_second, m->err, stream);
+  if (rc) return mfail(rc, "launch failed");
+  return m->errm.mark((hipStream_t)stream) ? mfail(ORBX_EDEVICE, "event record failed") : ORBX_OK;
+}
+
+int orbm_search_for_initialization_batch(orbm_handle m, const orbx_kp* d_kp1, const uint8_t* d_desc1,
+                                         const int* d_n1, const orbx_kp* d_kp2, const uint8_t* d_desc2,
+                                         const int* d_n2, int kp_pitch, int pairs, orbm_grid_bounds b,
+                                         float* d_prev_xy, int window, float nnratio, int check_ori,
+                                         int* d_matches12, int* d_nmatches, void* stream) {
+  if (!m || pairs < 1 || pairs > m->max_pairs || kp_pitch < 1 || kp_pitch > m->max_kps)
+    return mfail(ORBX_EINVAL, "pairs/kp_pitch exceed the matcher workspace");
+  MHIP(hipSetDevice(m->device));
+  return search_init_launch(m, d_kp1, d_desc1, d_n1, d_kp2, d_desc2, d_n2, kp_pitch, pairs, b, d_prev_xy, window,
+                            nnratio, check_ori, d_matches12, d_nmatches, stream, m->init_ws);
+}
+
+int orbm_search_for_initialization(orbm_handle m, const orbx_kp* kp1, const uint8_t* desc1, int n1,
+                                   const orbx_kp* kp2, const uint8_t* desc2, int n2, orbm_grid_bounds bounds,
+                                   float* prev_xy, int window, float nnratio, int check_ori, int* matches12,
+                                   int* nmatches) {
+  if (!m || !nmatches || n1 < 0 || n2 < 0) return mfail(ORBX_EINVAL, "bad argument");
+  if ((n1 && (!kp1 || !desc1 || !prev_xy || !matches12)) || (n2 && (!kp2 || !desc2)))
+    return mfail(ORBX_EINVAL, "null array");
+  MHIP(hipSetDevice(m->device));
+  // Only octave-0 keypoints take part (src/ORBmatcher.cc:424-428: level1 > 0 is
+  // skipped; GetFeaturesInArea(.., level1, level1) returns octave-0 keypoints of
+  // F2, src/Frame.cc:350-352), so both frames are compacted to them in index
+  // order before the upload: the kernel's per-keypoint tables then scale with
+  // the octave-0 counts, not with the frames' sizes, and every result maps back
+  // through the index lists. Other keypoints keep matches12 = -1 and their
+  // vbPrevMatched entry.
+  std::vector<int> q1, q2;
+  q1.reserve(n1);
+  q2.reserve(n2);
+  for (int i = 0; i < n1; ++i)
+    if (kp1[i].octave == 0) q1.push_back(i);
+  for (int i = 0; i < n2; ++i)
+    if (kp2[i].octave == 0) q2.push_back(i);
+  const int c1 = (int)q1.size(), c2 = (int)q2.size();
+  for (int i = 0; i < n1; ++i) matches12[i] = -1;
+  if (c1 == 0 || c2 == 0) {
+    *nmatches = 0;
+    return ORBX_OK;
+  }
+  const int pitch = std::max(c1, c2);
+  if (pitch > 65535) return mfail(ORBX_ECAPACITY, "more than 65535 octave-0 keypoints");
+  std::vector<orbx_kp> hk((size_t)c1 + c2);
+  std::vector<uint8_t> hd(((size_t)c1 + c2) * 32);
+  std::vector<float> hp((size_t)c1 * 2);
+  for (int k = 0; k < c1; ++k) {
+    hk[k] = kp1[q1[k]];
+    memcpy(&hd[(size_t)k * 32], desc1 + (size_t)q1[k] * 32, 32);
+    hp[2 * k] = prev_xy[2 * q1[k]];
+    hp[2 * k + 1] = prev_xy[2 * q1[k] + 1];
+  }
+  for (int k = 0; k < c2; ++k) {
+    hk[c1 + k] = kp2[q2[k]];
+    memcpy(&hd[((size_t)c1 + k) * 32], desc2 + (size_t)q2[k] * 32, 32);
+  }
+  const int hn[2] = {c1, c2};
+  int nm = 0, rc;
+  std::vector<int> hm(c1);
+  Stage st(m);  // after the host arrays: an error exit waits for the copies that use them
+  auto dk1 = st.slot<orbx_kp>(pitch), dk2 = st.slot<orbx_kp>(pitch);
+  auto dd1 = st.slot<uint8_t>((size_t)pitch * 32), dd2 = st.slot<uint8_t>((size_t)pitch * 32);
+  auto dprev = st.slot<float>((size_t)pitch * 2);
+  auto dm = st.slot<int>(pitch);
+  auto dn = st.slot<int>(2);  // n1, n2
+  auto dnm = st.slot<int>(1);
+  if ((rc = st.reserve()) || (rc = st.up(dk1, hk.data(), c1)) || (rc = st.up(dd1, hd.data(), (size_t)c1 * 32)) ||
+      (rc = st.up(dprev, hp.data(), (size_t)c1 * 2)) || (rc = st.up(dk2, hk.data() + c1, c2)) ||
+      (rc = st.up(dd2, hd.data() + (size_t)c1 * 32, (size_t)c2 * 32)) || (rc = st.up(dn, hn, 2)))
+    return rc;
+  // the call's own workspace, sized for its pitch (the octave-0 counts)
+  const size_t wsb = init_ws_bytes_per_pair(pitch);
+  if (wsb > m->host_init_ws_bytes) {
+    if (m->host_init_ws) {
+      MHIP(hipStreamSynchronize(st.st));
+      (void)hipFree(m->host_init_ws);
+    }
+    m->host_init_ws = nullptr;
+    m->host_init_ws_bytes = 0;
+    MHIP(hipMalloc(&m->host_init_ws, wsb));
+    m->host_init_ws_bytes = wsb;
+  }
+  rc = search_init_launch(m, dk1, dd1, dn, dk2, dd2, dn + 1, pitch, 1, bounds, dprev, window, nnratio, check_ori, dm,
+                          dnm, st.st, m->host_init_ws);
+  if (rc || (rc = st.down(&nm, dnm, 1)) || (rc = st.down(hm.data(), dm, c1)) ||
+      (rc = st.down(hp.data(), dprev, (size_t)c1 * 2)) || (rc = st.finish()))
+    return rc;
+  for (int k = 0; k < c1; ++k) {
+    const int i1 = q1[k];
+    matches12[i1] = hm[k] >= 0 ? q2[hm[k]] : -1;
+    prev_xy[2 * i1] = hp[2 * k];  // written by the kernel for matched queries, else the uploaded value
+    prev_xy[2 * i1 + 1] = hp[2 * k + 1];
+  }
+  *nmatches = nm;
+  return ORBX_OK;
+}
+
+int orbm_search_by_bow(orbm_handle m, const uint8_t* descA, const float* angleA, const uint8_t* mpA, int nA,
+                       orbm_feature_vector fvA, const uint8_t* descB, const float* angleB, const uint8_t* mpB,
+                       int nB, orbm_feature_vector fvB, float nnratio, int check_ori, int kf_vs_kf, int* out,
+                       int* nmatches) {
+  if (!m || !nmatches || nA < 0 || nB < 0) return mfail(ORBX_EINVAL, "bad argument");
+  // DBoW2 precondition: each feature sits in at most one node; node ids ascending
+  auto check_fv = [&](const orbm_feature_vector& fv, int n) -> bool {
+    std::vector<char> seen(std::max(n, 1), 0);
+    for (int k = 0; k < fv.n_nodes; ++k) {
+      if (k && fv.nodes[k] <= fv.nodes[k - 1]) return false;
+      for (int p = fv.off[k]; p < fv.off[k + 1]; ++p) {
+        const int i = fv.idx[p];
+        if (i < 0 || i >= n || seen[i]) return false;
+        seen[i] = 1;
+      }
+    }
+    return true;
+  };
+  // the row records keep the matched index in 16 bits (bin << 16 | index):
+  // B's index in KF-KF mode, A's in KF-Frame mode; B's candidates are 16-bit too
+  if (nB > 65536) return mfail(ORBX_EINVAL, "nB must be <= 65536");
+  if (!kf_vs_kf && nA > 65536) return mfail(ORBX_EINVAL, "nA must be <= 65536 (KF-Frame row records)");
+  if (!check_fv(fvA, nA) || !check_fv(fvB, nB))
+    return mfail(ORBX_EINVAL, "FeatureVector must have ascending node ids and disjoint in-range indices");
+  MHIP(hipSetDevice(m->device));
+  const int nout = kf_vs_kf ? nA : nB;
+  const int ia = fvA.n_nodes ? fvA.off[fvA.n_nodes] : 0, ib = fvB.n_nodes ? fvB.off[fvB.n_nodes] : 0;
+  const int pitch = std::max(nout, 1);  // out / records: the launch's pitch
+  const int hn[4] = {nA, nB, fvA.n_nodes, fvB.n_nodes};
+  int nm = 0, rc;
+  Stage st(m);
+  auto ddA = st.slot<uint8_t>((size_t)nA * 32), ddB = st.slot<uint8_t>((size_t)nB * 32);  // descriptors
+  auto dgA = st.slot<float>(nA), dgB = st.slot<float>(nB);                                // angles
+  auto dmA = st.slot<uint8_t>(nA), dmB = st.slot<uint8_t>(nB);                            // MapPoint masks
+  auto dnoA = st.slot<uint32_t>(fvA.n_nodes), dnoB = st.slot<uint32_t>(fvB.n_nodes);      // FeatureVector CSR
+  auto dofA = st.slot<int>(fvA.n_nodes + 1), dofB = st.slot<int>(fvB.n_nodes + 1);
+  auto dixA = st.slot<int>(ia), dixB = st.slot<int>(ib);
+  auto dout = st.slot<int>(pitch), drec = st.slot<int>(pitch);
+  auto dnm = st.slot<int>(1);
+  auto dn = st.slot<int>(4);  // nA, nB, nodes of A, nodes of B
+  auto dhist = st.slot<int>(32);
+  if ((rc = st.reserve()) || (rc = st.up(ddA, descA, (size_t)nA * 32)) || (rc = st.up(dgA, angleA, nA)) ||
+      (rc = st.up(dmA, mpA, nA)) || (rc = st.up(dnoA, fvA.nodes, fvA.n_nodes)) ||
+      (rc = st.up(dofA, fvA.off, fvA.n_nodes + 1)) || (rc = st.up(dixA, fvA.idx, ia)) ||
+      (rc = st.up(ddB, descB, (size_t)nB * 32)) || (rc = st.up(dgB, angleB, nB)) || (rc = st.up(dmB, mpB, nB)) ||
+      (rc = st.up(dnoB, fvB.nodes, fvB.n_nodes)) || (rc = st.up(dofB, fvB.off, fvB.n_nodes + 1)) ||
+      (rc = st.up(dixB, fvB.idx, ib)) || (rc = st.up(dn, hn, 4)))
+    return rc;
+  BowSide A{ddA, dgA, 1, mpA ? (uint8_t*)dmA : nullptr, dn, dnoA, dofA, dixA, dn + 2, 0, 0};
+  BowSide B{ddB, dgB, 1, mpB ? (uint8_t*)dmB : nullptr, dn + 1, dnoB, dofB, dixB, dn + 3, 0, 0};
+  bool clean = false;  // staging memory: records and histogram filled first
+  if ((rc = launch_search_bow(A, B, 1, nnratio, check_ori, kf_vs_kf, dout, pitch, dnm, drec, (size_t)pitch, dhist, 32,
+                              &clean, m->err, st.st)))
+    return mfail(rc, "search_bow launch: %s", hipGetErrorString(hipGetLastError()));
+  if (m->errm.mark(st.st)) return mfail(ORBX_EDEVICE, "event record failed");
+  if ((rc = st.down(&nm, dnm, 1)) || (rc = st.down(out, dout, nout)) || (rc = st.finish())) return rc;
+  *nmatches = nm;
+  return ORBX_OK;
+}
+
+int orbm_search_by_bow_batch(orbm_handle m, int pairs, int kp_pitch, int node_pitch, const orbx_kp* d_kpA,
+                             const uint8_t* d_descA, const int* d_nA, const uint8_t* d_mpA, const uint32_t* d_nodesA,
+                             const int* d_offA, const int* d_idxA, const int* d_nnA, const orbx_kp* d_kpB,
+                             const uint8_t* d_descB, const int* d_nB, const uint8_t* d_mpB, const uint32_t* d_nodesB,
+                             const int* d_offB, const int* d_idxB, const int* d_nnB, float nnratio, int check_ori,
+                             int kf_vs_kf, int* d_out, int* d_nmatches, void* stream) {
+  if (!m || pairs < 1 || kp_pitch < 1 || node_pitch < 1 || !d_kpA || !d_descA || !d_nA || !d_nodesA || !d_offA ||
+      !d_idxA || !d_nnA || !d_kpB || !d_descB || !d_nB || !d_nodesB || !d_offB || !d_idxB || !d_nnB || !d_out ||
+      !d_nmatches)
+    return mfail(ORBX_EINVAL, "bad argument");
+  if (pairs > m->max_pairs || kp_pitch > m->max_kps)
+    return mfail(ORBX_ECAPACITY, "pairs/kp_pitch above the matcher's max_pairs/max_kps");
+  if (kp_pitch > 65536) return mfail(ORBX_EINVAL, "kp_pitch must be <= 65536");
+  MHIP(hipSetDevice(m->device));
+  // angles straight from the orbx_kp records (cv::KeyPoint::angle, float 3 of 7)
+  BowSide A{d_descA, (const float*)d_kpA + 3, 7, d_mpA, d_nA, d_nodesA, d_offA, d_idxA, d_nnA, kp_pitch, node_pitch};
+  BowSide B{d_descB, (const float*)d_kpB + 3, 7, d_mpB, d_nB, d_nodesB, d_offB, d_idxB, d_nnB, kp_pitch, node_pitch};
+  hipStream_t s = (hipStream_t)stream;
+  if (m->ws.before(s)) return mfail(ORBX_EDEVICE, "stream wait on the workspace failed");
+  const int rc = launch_search_bow(A, B, pairs, nnratio, check_ori, kf_vs_kf, d_out, kp_pitch, d_nmatches, m->bow_rec,
+                                   (size_t)m->max_pairs * m->max_kps, m->bow_hist, (size_t)m->max_pairs * 32,
+                                   &m->bow_clean, m->err, stream);
+  if (rc) return mfail(rc, "search_bow launch: %s", hipGetErrorString(hipGetLastError()));
+  if (m->ws.after(s) || m->errm.mark(s)) return mfail(ORBX_EDEVICE, "event record failed");
+  return ORBX_OK;
+}
+
+// sync: a synchronous caller that waits for the launch itself: its
+// workspaces' earlier users are waited for only if still running, and no
+// event is recorded after it (no barrier packets around its kernels)
+static int stereo_batch(orbm_handle m, orbx_handle left, int left_frame0, orbx_handle right, int right_frame0,
+                        const orbx_kp* d_kpL, const uint8_t* d_descL, const int* d_nL, const orbx_kp* d_kpR,
+                        const uint8_t* d_descR, const int* d_nR, int kp_pitch, int pairs, float mb, float mbf,
+                        float* d_uRight, float* d_depth, int* d_nkept, void* stream, bool sync) {
+  if (!m || !left || !right || !d_kpL || !d_descL || !d_nL || !d_kpR || !d_descR || !d_nR || !d_uRight ||
+      !d_depth || !d_nkept || pairs < 1 || kp_pitch < 1)
+    return mfail(ORBX_EINVAL, "bad argument");
+  if (pairs > m->max_pairs || kp_pitch > m->max_kps)
+    return mfail(ORBX_ECAPACITY, "pairs/kp_pitch above the matcher's max_pairs/max_kps");
+  if (!(mb > 0.f)) return mfail(ORBX_EINVAL, "baseline mb must be positive");
+  MHIP(hipSetDevice(m->device));
+  StereoParams P{};
+  int wr[kMaxLevels], hr[kMaxLevels], LR = 0;
+  float sr[kMaxLevels], isr[kMaxLevels];
+  if (extractor_pyramid(left, left_frame0, pairs, &P.pl, P.lw, P.lh, P.scale, P.inv_scale, &P.L) ||
+      extractor_pyramid(right, right_frame0, pairs, &P.pr, wr, hr, sr, isr, &LR))
+    return mfail(ORBX_EINVAL, "stereo pyramid: %s", orbx_last_error());
+  if (LR != P.L) return mfail(ORBX_EINVAL, "left and right extractors have different level counts");
+  for (int l = 0; l < P.L; ++l)
+    if (wr[l] != P.lw[l] || hr[l] != P.lh[l]) return mfail(ORBX_EINVAL, "left and right image sizes differ");
+  P.nrows = P.lh[0];
+  P.kp_pitch = kp_pitch;
+  P.mb = mb;
+  P.mbf = mbf;
+  // ~256 workgroups (one per CU) over the batch, 8 per pair for batches of
+  // 32+ pairs; each stages its pair's right keypoints and descriptors in LDS.
+  // Few pairs (the stereo Frame's one) take up to 64 per pair: the left
+  // keypoints each wave walks through one after another set the latency
+  // (one pair: 0.107 ms with 8, 0.085 ms with 64, shim_latency's stereo_parts)
+  P.groups = std::max(1, std::min(64, (256 + pairs - 1) / pairs));
+  if (const char* e = getenv("ORBX_STEREO_GROUPS")) P.groups = std::max(1, atoi(e));  // tuning experiments
+  P.stop = 0;
+#ifdef ORBX_DIAG  // diagnostics builds only: stop after a phase, results incomplete
+  if (const char* e = getenv("ORBX_STEREO_STOP")) P.stop = atoi(e);
+#endif
+  // workgroup g takes left keypoints iL = g + groups * m: at most this many
+  P.jobs_cap = (kp_pitch + P.groups - 1) / P.groups;
+  if (stereo_lds_bytes(P.nrows, kp_pitch, P.jobs_cap) > 156 * 1024)
+    return mfail(ORBX_ECAPACITY, "stereo row table does not fit in LDS (rows %d, kp_pitch %d)", P.nrows, kp_pitch);
+  // the SAD scratch is the matcher's, the pyramids the extractors': order
+  // this launch after their last users and make their next users wait for it
+  hipStream_t s = (hipStream_t)stream;
+  WsOrder* wl = extractor_ws(left);
+  WsOrder* wr2 = extractor_ws(right);
+  if (sync ? (m->ws.before_pending(s) || wl->before_pending(s) || wr2->before_pending(s))
+           : (m->ws.before(s) || wl->before(s) || wr2->before(s)))
+    return mfail(ORBX_EDEVICE, "stream wait on the workspaces failed");
+  if (launch_stereo(P, d_kpL, d_descL, d_nL, d_kpR, d_descR, d_nR, pairs, d_uRight, d_depth, m->stereo_sad, d_nkept,
+                    stream) != ORBX_OK)
+    return mfail(ORBX_EDEVICE, "stereo launch: %s", hipGetErrorString(hipGetLastError()));
+  if (!sync && (m->ws.after(s) || wl->after(s) || wr2->after(s))) return mfail(ORBX_EDEVICE, "event record failed");
+  return ORBX_OK;
+}
+
+int orbm_compute_stereo_matches_batch(orbm_handle m, orbx_handle left, int left_frame0, orbx_handle right,
+                                      int right_frame0, const orbx_kp* d_kpL, const uint8_t* d_descL,
+                                      const int* d_nL, const orbx_kp* d_kpR, const uint8_t* d_descR,
+                                      const int* d_nR, int kp_pitch, int pairs, float mb, float mbf,
+                                      float* d_uRight, float* d_depth, int* d_nkept, void* stream) {
+  return stereo_batch(m, left, left_frame0, right, right_frame0, d_kpL, d_descL, d_nL, d_kpR, d_descR, d_nR,
+                      kp_pitch, pairs, mb, mbf, d_uRight, d_depth, d_nkept, stream, false);
+}
+
+int orbm_compute_stereo_matches(orbm_handle m, orbx_handle left, orbx_handle right, const orbx_kp* kpL,
+                                const uint8_t* descL, int nL, const orbx_kp* kpR, const uint8_t* descR, int nR,
+                                float mb, float mbf, float* uRight, float* depth, int* nkept) {
+  if (!m || !nkept || nL < 0 || nR < 0 || (nL && (!kpL || !descL || !uRight || !depth)) || (nR && (!kpR || !descR)))
+    return mfail(ORBX_EINVAL, "bad argument");
+  if (nL > m->max_kps || nR > m->max_kps) return mfail(ORBX_ECAPACITY, "more keypoints than max_kps");
+  if (nR > 65535) return mfail(ORBX_ECAPACITY, "more than 65535 right keypoints");
+  MHIP(hipSetDevice(m->device));
+  const int pitch = std::max(std::max(nL, nR), 1);
+  const int hn[2] = {nL, nR};
+  int kept = 0, rc;
+  Stage st(m);
+  auto dkl = st.slot<orbx_kp>(pitch), dkr = st.slot<orbx_kp>(pitch);
+  auto ddl = st.slot<uint8_t>((size_t)pitch * 32), ddr = st.slot<uint8_t>((size_t)pitch * 32);
+  auto du = st.slot<float>(pitch), dd = st.slot<float>(pitch);
+  auto dn = st.slot<int>(2);  // nL, nR
+  auto dkept = st.slot<int>(1);
+  if ((rc = st.reserve()) || (rc = st.up(dkl, kpL, nL)) || (rc = st.up(ddl, descL, (size_t)nL * 32)) ||
+      (rc = st.up(dkr, kpR, nR)) || (rc = st.up(ddr, descR, (size_t)nR * 32)) || (rc = st.up(dn, hn, 2)) ||
+      (rc = stereo_batch(m, left, 0, right, 0, dkl, ddl, dn, dkr, ddr, dn + 1, pitch, 1, mb, mbf, du, dd, dkept, st.st,
+                         true)) ||
+      (rc = st.down(&kept, dkept, 1)) || (rc = st.down(uRight, du, nL)) || (rc = st.down(depth, dd, nL)) ||
+      (rc = st.finish()))
+    return rc;
+  *nkept = kept;
+  return ORBX_OK;
+}
+
+// The stereo kernels' outputs {kept, -, -, -, uRight[cap], depth[cap]} in one
+// block at the head of the arena (cap = the kernels' pitch), so that one copy
+// brings them into the matcher's pinned staging.
+struct StereoBlock {
+  int* kept;
+  float *uRight, *depth;  // device
+  size_t bytes;
+  static int reserve(orbx_matcher* m, int cap, StereoBlock* b) {
+    b->bytes = 16 + (size_t)cap * 8;
+    int rc;
+    if ((rc = stage_reserve(m, b->bytes)) || (rc = host_stage_reserve(m, b->bytes))) return rc;
+    b->kept = (int*)m->stage;
+    b->uRight = (float*)m->stage + 4;
+    b->depth = b->uRight + cap;
+    return ORBX_OK;
+  }
+  // from the pinned copy, the first nL of each array
+  static void unpack(const orbx_matcher* m, int cap, int nL, float* uRight, float* depth, int* nkept) {
+    const uint8_t* h = (const uint8_t*)m->h_stage;
+    *nkept = ((const int*)h)[0];
+    if (nL) {
+      memcpy(uRight, h + 16, (size_t)nL * 4);
+      memcpy(depth, h + 16 + (size_t)cap * 4, (size_t)nL * 4);
+    }
+  }
+};
+
+// Frame::ComputeStereoMatches right after the stereo constructor's two
+// extractions (src/Frame.cc:77-89): the keypoints and descriptors are read
+// where the two orbx_extract calls left them on the device, so only mvuRight
+// and mvDepth cross the link.
+int orbm_compute_stereo_matches_last(orbm_handle m, orbx_handle left, orbx_handle right, float mb, float mbf,
+                                     float* uRight, float* depth, int nL, int* nkept) {
+  if (!m || !left || !right || !nkept || nL < 0 || (nL && (!uRight || !depth))) return mfail(ORBX_EINVAL, "bad argument");
+  const int* dnL = nullptr;
+  const int* dnR = nullptr;
+  const orbx_kp *dkl = nullptr, *dkr = nullptr;
+  const uint8_t *ddl = nullptr, *ddr = nullptr;
+  int capL = 0, capR = 0;
+  if (extractor_last_output(left, &dnL, &dkl, &ddl, &capL) || extractor_last_output(right, &dnR, &dkr, &ddr, &capR))
+    return mfail(ORBX_EINVAL, "stereo (last extraction): %s", orbx_last_error());
+  if (!dnL || !dnR) {
+    // an empty left or right image: no right keypoints to match, every left
+    // keypoint keeps uRight = depth = -1 (src/Frame.cc:465-470)
+    if (!dnL && nL) return mfail(ORBX_EINVAL, "nL %d but the left extraction was of an empty image", nL);
+    for (int i = 0; i < nL; ++i) uRight[i] = depth[i] = -1.f;
+    *nkept = 0;
+    return ORBX_OK;
+  }
+  if (capL != capR) return mfail(ORBX_EINVAL, "left and right extractors have different capacities");
+  if (nL > capL) return mfail(ORBX_EINVAL, "nL %d above the left extraction's capacity %d", nL, capL);
+  MHIP(hipSetDevice(m->device));
+  // the device path sizes its LDS by the extractors' capacity; past the
+  // matcher's limits (max_kps, or the stereo kernel's LDS for large
+  // nFeatures) the keypoints come to the host and take the host-array path,
+  // whose pitch is the actual counts
+  auto host_fallback = [&]() -> int {
+    int cnt[2] = {0, 0};
+    MHIP(hipMemcpy(&cnt[0], dnL, 4, hipMemcpyDeviceToHost));
+    MHIP(hipMemcpy(&cnt[1], dnR, 4, hipMemcpyDeviceToHost));
+    if (nL > cnt[0]) return mfail(ORBX_EINVAL, "nL %d above the left extraction's count %d", nL, cnt[0]);
+    std::vector<orbx_kp> kl(std::max(cnt[0], 1)), kr(std::max(cnt[1], 1));
+    std::vector<uint8_t> dl((size_t)std::max(cnt[0], 1) * 32), dr((size_t)std::max(cnt[1], 1) * 32);
+    MHIP(hipMemcpy(kl.data(), dkl, (size_t)cnt[0] * sizeof(orbx_kp), hipMemcpyDeviceToHost));
+    MHIP(hipMemcpy(kr.data(), dkr, (size_t)cnt[1] * sizeof(orbx_kp), hipMemcpyDeviceToHost));
+    MHIP(hipMemcpy(dl.data(), ddl, (size_t)cnt[0] * 32, hipMemcpyDeviceToHost));
+    MHIP(hipMemcpy(dr.data(), ddr, (size_t)cnt[1] * 32, hipMemcpyDeviceToHost));
+    return orbm_compute_stereo_matches(m, left, right, kl.data(), dl.data(), nL, kr.data(), dr.data(), cnt[1], mb, mbf,
+                                       uRight, depth, nkept);
+  };
+  if (capL > m->max_kps) return host_fallback();
+  StereoBlock blk;
+  Stage st(m);
+  int rc;
+  if ((rc = StereoBlock::reserve(m, capL, &blk)) || (rc = st.open())) return rc;
+  rc = stereo_batch(m, left, 0, right, 0, dkl, ddl, dnL, dkr, ddr, dnR, capL, 1, mb, mbf, blk.uRight, blk.depth,
+                    blk.kept, st.st, true);
+  if (rc == ORBX_ECAPACITY) return host_fallback();  // checked before any launch
+  st.pending = true;  // no upload went before: the kernels count as enqueued even where stereo_batch failed
+  if (rc || (rc = st.copy(m->h_stage, blk.kept, blk.bytes, hipMemcpyDeviceToHost)) || (rc = st.finish())) return rc;
+  StereoBlock::unpack(m, capL, nL, uRight, depth, nkept);
+  return ORBX_OK;
+}
+
+// orbm_stereo_frame's host phases (ORBX_STEREO_PROF=1): left staged, issued,
+// right staged, issued, stereo issued, waited, copied out; medians of the
+// calls after the first 20 per left handle, printed at exit
+struct StereoProf {
+  std::mutex mu;
+  std::vector<std::pair<const void*, std::vector<double>>> per;  // per left handle: 7 phases per call
+  void add(const void* key, const double* st) {
+    std::lock_guard<std::mutex> lk(mu);
+    size_t i = 0;
+    while (i < per.size() && per[i].first != key) ++i;
+    if (i == per.size()) per.push_back({key, {}});
+    for (int k = 0; k < 7; ++k) per[i].second.push_back(st[k + 1] - st[k]);
+  }
+  ~StereoProf() {
+    const char* names[7] = {"left staged", "issued", "right staged", "issued", "stereo issued", "wait", "copy-out"};
+    for (auto& e : per) {
+      const size_t n = e.second.size() / 7;
+      if (n <= 20) continue;
+      fprintf(stderr, "orbm_stereo_frame host phases, median of %zu calls (us):", n - 20);
+      for (int k = 0; k < 7; ++k) {
+        std::vector<double> v;
+        for (size_t c = 20; c < n; ++c) v.push_back(e.second[c * 7 + k]);
+        std::nth_element(v.begin(), v.begin() + v.size() / 2, v.end());
+        fprintf(stderr, " %s %.1f", names[k], v[v.size() / 2] * 1e6);
+      }
+      fprintf(stderr, "\n");
+    }
+  }
+};
+static StereoProf& stereo_prof() {
+  static StereoProf p;
+  return p;
+}
+
+// The stereo Frame's construction steps (src/Frame.cc:77-89: ExtractORB on
+// threadLeft / threadRight, then ComputeStereoMatches :465-639) with one
+// device round trip: both extraction chains are issued from the calling
+// thread on the two handles' streams (they run concurrently), the stereo
+// kernels follow on the right stream once both are done, and their {kept,
+// uRight, depth} block comes back (a copy kernel into pinned memory) in the
+// same wait as the two extractions' outputs. Results are those of
+// orbx_extract x2 + orbm_compute_stereo_matches_last.
+int orbm_stereo_frame(orbm_handle m, orbx_handle left, orbx_handle right, const uint8_t* img_left,
+                      size_t stride_left, const uint8_t* img_right, size_t stride_right, int w, int h, float mb,
+                      float mbf, orbx_kp* kps_left, int cap_left, uint8_t* desc_left, int* n_left,
+                      orbx_kp* kps_right, int cap_right, uint8_t* desc_right, int* n_right, float* uRight,
+                      float* depth, int* nkept) {
+  if (!m || !left || !right || !n_left || !n_right || !nkept || w < 0 || h < 0) return mfail(ORBX_EINVAL, "bad argument");
+  if (left == right) return mfail(ORBX_EINVAL, "left and right need two extractor handles");
+  if (!(mb > 0.f)) return mfail(ORBX_EINVAL, "baseline mb must be positive");
+  *nkept = 0;
+  if (w == 0 || h == 0) {
+    // empty images: the two calls' own semantics (no outputs, uRight = -1)
+    if (orbx_extract(left, img_left, w, h, stride_left, kps_left, cap_left, desc_left, n_left) ||
+        orbx_extract(right, img_right, w, h, stride_right, kps_right, cap_right, desc_right, n_right))
+      return mfail(ORBX_EINVAL, "stereo frame: %s", orbx_last_error());
+    return orbm_compute_stereo_matches_last(m, left, right, mb, mbf, uRight, depth, *n_left, nkept);
+  }
+  MHIP(hipSetDevice(m->device));
+  int brc = ORBX_OK, cap = 0;
+  auto between = [&](hipStream_t st) -> int {
+    const int* dnL = nullptr;
+    const int* dnR = nullptr;
+    const orbx_kp *dkl = nullptr, *dkr = nullptr;
+    const uint8_t *ddl = nullptr, *ddr = nullptr;
+    int capR = 0;
+    if (extractor_last_output(left, &dnL, &dkl, &ddl, &cap) || extractor_last_output(right, &dnR, &dkr, &ddr, &capR))
+      return brc = mfail(ORBX_EINVAL, "stereo frame: %s", orbx_last_error());
+    if (cap != capR) return brc = mfail(ORBX_EINVAL, "left and right extractors have different capacities");
+    // past the matcher's limits: the host-array path after the extractions
+    if (cap > m->max_kps) return (brc = ORBX_ECAPACITY), ORBX_OK;
+    StereoBlock blk;
+    int rc;
+    if ((rc = StereoBlock::reserve(m, cap, &blk))) return brc = rc;
+    rc = stereo_batch(m, left, 0, right, 0, dkl, ddl, dnL, dkr, ddr, dnR, cap, 1, mb, mbf, blk.uRight, blk.depth,
+                      blk.kept, st, true);
+    if (rc == ORBX_ECAPACITY) return (brc = ORBX_ECAPACITY), ORBX_OK;  // checked before any launch
+    if (rc) return brc = rc;
+    if ((rc = copy_to_host_async(m->h_stage, blk.kept, blk.bytes, st))) return brc = mfail(rc, "%s", orbx_last_error());
+    return ORBX_OK;
+  };
+  // ORBX_STEREO_PROF=1 (diagnostics): host phases per call, medians printed at exit
+  static const bool prof = getenv("ORBX_STEREO_PROF") && getenv("ORBX_STEREO_PROF")[0] == '1';
+  double st[8];
+  if (prof) st[0] = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+  int rc = extract_pair(left, right, img_left, stride_left, img_right, stride_right, w, h, between, kps_left, cap_left,
+                        desc_left, n_left, kps_right, cap_right, desc_right, n_right, prof ? st + 1 : nullptr);
+  if (prof && !rc) stereo_prof().add(left, st);
+  if (rc) return brc ? brc : mfail(rc, "stereo frame: %s", orbx_last_error());
+  if (brc == ORBX_ECAPACITY)
+    return orbm_compute_stereo_matches_last(m, left, right, mb, mbf, uRight, depth, *n_left, nkept);
+  if (brc) return brc;
+  const int nL = *n_left;
+  const bool no_out = nL && (!uRight || !depth);
+  StereoBlock::unpack(m, cap, no_out ? 0 : nL, uRight, depth, nkept);
+  return no_out ? mfail(ORBX_EINVAL, "null uRight/depth") : ORBX_OK;
+}
+
+int orbm_search_by_projection_batch(orbm_handle m, const orbx_kp* d_kps, const uint8_t* d_desc, const int* d_n,
+                                    int kp_pitch, const float* d_uright, orbm_grid_bounds b, const float* scale,
+                                    int nlevels, const uint8_t* d_blocked, const orbm_map_point_proj* d_mps,
+                                    const uint8_t* d_mpdesc, const int* d_nmp, int mp_pitch, int frames, float th,
+                                    float nnratio, int* d_out, int* d_nmatches, void* stream) {
+  if (!m || !d_kps || !d_desc || !d_n || !scale || !d_blocked || !d_mps || !d_mpdesc || !d_nmp || !d_out ||
+      !d_nmatches || frames < 1 || kp_pitch < 1 || mp_pitch < 1 || nlevels < 1 || nlevels > kMaxLevels)
+    return mfail(ORBX_EINVAL, "bad argument");
+  if (mp_pitch > 8192) return mfail(ORBX_ECAPACITY, "more than 8192 map points per frame");
+  if (!(b.max_x > b.min_x) || !(b.max_y > b.min_y)) return mfail(ORBX_EINVAL, "empty grid bounds");
+  if (proj_lds_bytes(kp_pitch) > 156 * 1024) return mfail(ORBX_ECAPACITY, "kp_pitch %d too large", kp_pitch);
+  MHIP(hipSetDevice(m->device));
+  ProjParams P{};
+  set_grid_bounds(P, b);
+  for (int l = 0; l < kMaxLevels; ++l) P.scale[l] = scale[std::min(l, nlevels - 1)];
+  P.th = th;
+  P.nnratio = nnratio;
+  P.kp_pitch = kp_pitch;
+  P.mp_pitch = mp_pitch;
+  P.has_uright = d_uright != nullptr;
+  P.max_rounds = 32;
+  if (const char* e = getenv("ORBX_PROJ_ROUNDS")) P.max_rounds = atoi(e);  // tests: force the sequential pass
+  static long long* prof = nullptr;  // ORBX_PROJ_PROF: phase clocks of frame 0 printed after the call
+  const bool do_prof = getenv("ORBX_PROJ_PROF") != nullptr;
+  if (do_prof) {
+    if (!prof) MHIP(hipMalloc(&prof, (size_t)frames * 64 * 8));
+    MHIP(hipMemset(prof, 0, (size_t)frames * 64 * 8));
+    P.prof = prof;
+  }
+  if (launch_search_proj(P, d_kps, d_desc, d_n, d_uright, d_blocked, d_mps, d_mpdesc, d_nmp, frames, d_out,
+                         d_nmatches, stream))
+    return mfail(ORBX_EDEVICE, "search_proj launch: %s", hipGetErrorString(hipGetLastError()));
+  if (do_prof) {
+    long long h[64];
+    MHIP(hipStreamSynchronize((hipStream_t)stream));
+    MHIP(hipMemcpy(h, prof, sizeof h, hipMemcpyDeviceToHost));
+    fprintf(stderr, "proj prof frame 0:");
+    for (int i = 1; i < 42 && h[i]; ++i) fprintf(stderr, " r%d=%lld", i - 1, h[i] - h[0]);
+    fprintf(stderr, "\n");
+  }
+  return ORBX_OK;
+}
+
+int orbm_search_by_projection(orbm_handle m, const orbx_kp* kps, const uint8_t* desc, int n, const float* uright,
+                              orbm_grid_bounds b, const float* scale, int nlevels, const uint8_t* blocked,
+                              const orbm_map_point_proj* mps, const uint8_t* mpdesc, int nmp, float th,
+                              float nnratio, int* out, int* nmatches) {
+  if (!m || !nmatches || n < 0 || nmp < 0 || (n && (!kps || !desc || !blocked || !out)) ||
+      (nmp && (!mps || !mpdesc)))
+    return mfail(ORBX_EINVAL, "bad argument");
+  if (nmp > 8192) return mfail(ORBX_ECAPACITY, "more than 8192 map points");
+  MHIP(hipSetDevice(m->device));
+  const int kp = std::max(n, 1), mp = std::max(nmp, 1);
+  const int hn[2] = {n, nmp};
+  int nm = 0, rc;
+  Stage st(m);
+  auto dk = st.slot<orbx_kp>(kp);
+  auto dd = st.slot<uint8_t>((size_t)kp * 32);
+  auto dur = st.slot<float>(kp);
+  auto dbl = st.slot<uint8_t>(kp);
+  auto dmp = st.slot<orbm_map_point_proj>(mp);
+  auto dmd = st.slot<uint8_t>((size_t)mp * 32);
+  auto dout = st.slot<int>(kp);
+  auto cnt = st.slot<int>(2);  // n, nmp
+  auto dnm = st.slot<int>(1);
+  if ((rc = st.reserve()) || (rc = st.up(dk, kps, n)) || (rc = st.up(dd, desc, (size_t)n * 32)) ||
+      (rc = st.up(dur, uright, n)) || (rc = st.up(dbl, blocked, n)) || (rc = st.up(dmp, mps, nmp)) ||
+      (rc = st.up(dmd, mpdesc, (size_t)nmp * 32)) || (rc = st.up(cnt, hn, 2)) ||
+      (rc = orbm_search_by_projection_batch(m, dk, dd, cnt, kp, uright ? (float*)dur : nullptr, b, scale, nlevels, dbl,
+                                            dmp, dmd, cnt + 1, mp, 1, th, nnratio, dout, dnm, st.st)) ||
+      (rc = st.down(&nm, dnm, 1)) || (rc = st.down(out, dout, n)) || (rc = st.finish()))
+    return rc;
+  *nmatches = nm;
+  return ORBX_OK;
+}
+
+// ---------------------------------------------- pose-projection overloads
+namespace {
+
+// R*x + t via gemm's small-matrix path (float dot, double add of t)
+void host_rx_t(const float* T, const float* x, float* d) {
+  for (int r = 0; r < 3; ++r) {
+    const float t = T[4 * r] * x[0] + T[4 * r + 1] * x[1] + T[4 * r + 2] * x[2];
+    d[r] = (float)((double)t * 1.0 + (double)T[4 * r + 3] * 1.0);
+  }
+}
+// -R.t()*t via the general gemm path (double accumulation)
+void host_neg_rt_t(const float* T, float* d) {
+  for (int r = 0; r < 3; ++r) {
+    double s = 0;
+    for (int k = 0; k < 3; ++k) s += (double)T[4 * k + r] * (double)T[4 * k + 3];
+    d[r] = (float)(s * -1.0);
+  }
+}
+// MapPoint::PredictScale's int level as a predicate of the ratio
+int host_predict_direct(float ratio, float logsf, int L) {
+  const float q = std::ceil(std::log(ratio) / logsf);  // float overloads (logf)
+  int s = (q >= -2147483648.0f && q < 2147483648.0f) ? (int)q : INT_MIN;
+  return s < 0 ? 0 : (s >= L ? L - 1 : s);
+}
+
+}  // namespace
+
+int orbm_prepare_pose(int mode, const orbm_camera* cam, const float* Tlw, int mono, orbm_pose* out) {
+  if (!cam || !out || mode < ORBM_PROJ_LAST_FRAME || mode > ORBM_PROJ_FUSE_SIM3 ||
+      (mode == ORBM_PROJ_LAST_FRAME && !Tlw))
+    return mfail(ORBX_EINVAL, "bad argument");
+  orbm_pose p{};
+  p.fx = cam->fx;
+  p.fy = cam->fy;
+  p.cx = cam->cx;
+  p.cy = cam->cy;
+  p.mbf = cam->mbf;
+  if (mode == ORBM_PROJ_SIM3 || mode == ORBM_PROJ_FUSE_SIM3) {
+    // scw = sqrt(sRcw.row(0).dot(sRcw.row(0))); Rcw = sRcw/scw; tcw = t/scw
+    // (src/ORBmatcher.cc:298-303, 986-991): Mat::dot in double, Mat / s = convertTo(1/s)
+    const float* S = cam->Tcw;
+    const double d = (double)S[0] * S[0] + (double)S[1] * S[1] + (double)S[2] * S[2];
+    const float scw = (float)std::sqrt(d);
+    if (!(scw > 0)) return mfail(ORBX_EINVAL, "Scw has a zero scale");
+    const float a = (float)(1.0 / (double)scw);
+    for (int k = 0; k < 12; ++k) p.Rt[k] = S[k] * a + 0.0f;
+  } else {
+    for (int k = 0; k < 12; ++k) p.Rt[k] = cam->Tcw[k];
+  }
+  host_neg_rt_t(p.Rt, p.Ow);  // Ow = -Rcw.t()*tcw
+  p.level_mode = 0;
+  if (mode == ORBM_PROJ_LAST_FRAME) {
+    // twc = -Rcw.t()*tcw; tlc = Rlw*twc + tlw (src/ORBmatcher.cc:1338-1349)
+    float tlc[3];
+    host_rx_t(Tlw, p.Ow, tlc);
+    const bool bForward = tlc[2] > cam->mb && !mono;
+    const bool bBackward = -tlc[2] > cam->mb && !mono;
+    p.level_mode = bForward ? 1 : (bBackward ? 2 : 0);
+  }
+  *out = p;
+  return ORBX_OK;
+}
+
+int orbm_prepare_sim3_match(const orbm_camera* cam1, const float* T1w, const float* T2w, float s12, const float* R12,
+                            const float* t12, orbm_pose* out) {
+  if (!cam1 || !T1w || !T2w || !R12 || !t12 || !out || !(s12 != 0.0f)) return mfail(ORBX_EINVAL, "bad argument");
+  // sR12 = s12*R12; sR21 = (1.0/s12)*R12.t(); t21 = -sR21*t12 (src/ORBmatcher.cc:1118-1120):
+  // scalar * Mat = convertTo(alpha) in float, -A*t = gemm small path with alpha -1
+  const float a12 = (float)(double)s12, a21 = (float)(1.0 / (double)s12);
+  float S12[12], S21[12];
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) {
+      S12[4 * r + c] = R12[3 * r + c] * a12 + 0.0f;
+      S21[4 * r + c] = R12[3 * c + r] * a21 + 0.0f;
+    }
+  for (int r = 0; r < 3; ++r) {
+    S12[4 * r + 3] = t12[r];
+    const float t = S21[4 * r] * t12[0] + S21[4 * r + 1] * t12[1] + S21[4 * r + 2] * t12[2];
+    S21[4 * r + 3] = (float)((double)t * -1.0 + 0.0 * 0.0);
+  }
+  for (int d = 0; d < 2; ++d) {
+    orbm_pose p{};
+    p.fx = cam1->fx;
+    p.fy = cam1->fy;
+    p.cx = cam1->cx;
+    p.cy = cam1->cy;
+    p.mbf = cam1->mbf;
+    std::memcpy(p.Rt, d == 0 ? T1w : T2w, sizeof p.Rt);
+    std::memcpy(p.Rt2, d == 0 ? S21 : S12, sizeof p.Rt2);
+    host_neg_rt_t(p.Rt, p.Ow);
+    out[d] = p;
+  }
+  return ORBX_OK;
+}
+
+int orbm_predict_scale_thresholds(float scale_factor, int nlevels, float* thr) {
+  if (!thr || nlevels < 1 || nlevels > kMaxLevels || !(scale_factor > 1.0f))
+    return mfail(ORBX_EINVAL, "bad argument");
+  const float logsf = std::log(scale_factor);  // Frame::mfLogScaleFactor (src/Frame.cc:70)
+  for (int k = 1; k < nlevels; ++k) {
+    // least positive float r with level(r) >= k; level is non-decreasing in r
+    uint32_t lo = 0x00000001u, hi = 0x7f7fffffu;  // level(lo) = 0 < k <= level(FLT_MAX)
+    auto at = [](uint32_t b) {
+      float f;
+      std::memcpy(&f, &b, 4);
+      return f;
+    };
+    if (host_predict_direct(at(hi), logsf, nlevels) < k) return mfail(ORBX_EINVAL, "scale factor too small");
+    while (hi - lo > 1) {
+      const uint32_t mid = lo + (hi - lo) / 2;
+      if (host_predict_direct(at(mid), logsf, nlevels) >= k)
+        hi = mid;
+      else
+        lo = mid;
+    }
+    thr[k - 1] = at(hi);
+  }
+  for (int k = nlevels; k <= kMaxLevels; ++k) thr[k - 1 < kMaxLevels ? k - 1 : 0] = INFINITY;
+  return ORBX_OK;
+}
+
+int orbm_predict_scale(float max_distance, float dist, float scale_factor, int nlevels) {
+  float thr[kMaxLevels];
+  if (orbm_predict_scale_thresholds(scale_factor, nlevels, thr)) return -1;
+  const float ratio = max_distance / dist;
+  if (std::isinf(ratio)) return 0;
+  int l = 0;
+  for (int k = 0; k < nlevels - 1; ++k) l += ratio >= thr[k];
+  return l;
+}
+
+int orbm_search_by_projection_pose_batch(orbm_handle m, int mode, const orbx_kp* d_kps, const uint8_t* d_desc,
+                                         const int* d_n, int kp_pitch, const float* d_uright, orbm_grid_bounds b,
+                                         const float* scale, int nlevels, float scale_factor,
+                                         const uint8_t* d_blocked, const orbm_pose* d_poses,
+                                         const orbm_map_point_world* d_mps, const uint8_t* d_mpdesc,
+                                         const int* d_nmp, int mp_pitch, int frames, float th, int dist_th,
+                                         int check_ori, const float* inv_sigma2, int* d_out, int* d_nmatches,
+                                         void* stream) {
+  if (!m || !d_kps || !d_desc || !d_n || !scale || !d_blocked || !d_poses || !d_mps || !d_mpdesc || !d_nmp ||
+      !d_out || !d_nmatches || frames < 1 || kp_pitch < 1 || mp_pitch < 1 || nlevels < 1 ||
+      nlevels > kMaxLevels || mode < ORBM_PROJ_LAST_FRAME || mode > ORBM_PROJ_SIM3_MATCH ||
+      (mode == ORBM_PROJ_FUSE && !inv_sigma2))
+    return mfail(ORBX_EINVAL, "bad argument");
+  if (!(b.max_x > b.min_x) || !(b.max_y > b.min_y)) return mfail(ORBX_EINVAL, "empty grid bounds");
+  if (pose_lds_bytes(kp_pitch) > 156 * 1024) return mfail(ORBX_ECAPACITY, "kp_pitch %d too large", kp_pitch);
+  MHIP(hipSetDevice(m->device));
+  PoseParams P{};
+  P.mode = mode;
+  set_grid_bounds(P, b);
+  for (int l = 0; l < kMaxLevels; ++l) P.scale[l] = scale[std::min(l, nlevels - 1)];
+  if (mode != ORBM_PROJ_LAST_FRAME) {
+    int rc = orbm_predict_scale_thresholds(scale_factor, nlevels, P.pred_thr);
+    if (rc) return rc;
+  }
+  P.L = nlevels;
+  P.th = th;
+  P.dist_th = dist_th;
+  P.check_ori = check_ori;
+  P.kp_pitch = kp_pitch;
+  P.mp_pitch = mp_pitch;
+  P.has_uright = d_uright != nullptr && (mode == ORBM_PROJ_LAST_FRAME || mode == ORBM_PROJ_FUSE);
+  for (int l = 0; l < kMaxLevels; ++l) P.inv_sigma2[l] = inv_sigma2 ? inv_sigma2[std::min(l, nlevels - 1)] : 0.f;
+  P.max_rounds = 32;
+  if (const char* e = getenv("ORBX_PROJ_ROUNDS")) P.max_rounds = atoi(e);  // tests: force the sequential pass
+  const size_t need = (size_t)frames * mp_pitch;
+  if (m->ws.before((hipStream_t)stream)) return mfail(ORBX_EDEVICE, "stream wait on the workspace failed");
+  if (m->pose_picks_cap < need) {
+    if (m->ws.ev) MHIP(hipEventSynchronize(m->ws.ev));
+    if (m->pose_picks) MHIP(hipFree(m->pose_picks));
+    m->pose_picks = nullptr;
+    m->pose_picks_cap = 0;
+    if (hipMalloc(&m->pose_picks, need * 4) != hipSuccess) return mfail(ORBX_ENOMEM, "pose picks workspace");
+    m->pose_picks_cap = need;
+  }
+  if (launch_search_pose(P, d_kps, d_desc, d_n, d_uright, d_blocked, d_poses, d_mps, d_mpdesc, d_nmp, frames,
+                         m->pose_picks, d_out, d_nmatches, stream))
+    return mfail(ORBX_EDEVICE, "search_pose launch: %s", hipGetErrorString(hipGetLastError()));
+  if (m->ws.after((hipStream_t)stream)) return mfail(ORBX_EDEVICE, "event record failed");
+  return ORBX_OK;
+}
+
+namespace {
+// One frame through orbm_search_by_projection_pose_batch from host buffers.
+int pose_sync(orbm_handle m, int mode, const orbx_kp* kps, const uint8_t* desc, int n, const float* uright,
+              orbm_grid_bounds b, const float* scale, int nlevels, float scale_factor, const uint8_t* blocked,
+              const orbm_pose& pose, const orbm_map_point_world* mps, const uint8_t* mpdesc, int nmp, float th,
+              int dist_th, int check_ori, int* out, int* nmatches, const float* inv_sigma2 = nullptr) {
+  const bool pp = mode == ORBM_PROJ_FUSE || mode == ORBM_PROJ_FUSE_SIM3 || mode == ORBM_PROJ_SIM3_MATCH;
+  if (!m || !nmatches || n < 0 || nmp < 0 || (n && (!kps || !desc)) || (nmp && (!mps || !mpdesc)) ||
+      ((pp ? nmp : n) && !out))
+    return mfail(ORBX_EINVAL, "bad argument");
+  MHIP(hipSetDevice(m->device));
+  const int kp = std::max(n, 1), mp = std::max(nmp, 1);
+  std::vector<uint8_t> bl(kp, 0);  // a null `blocked` uploads zeros
+  if (blocked && n) std::memcpy(bl.data(), blocked, n);
+  const int hn[2] = {n, nmp};
+  int nm = 0, rc;
+  Stage st(m);
+  auto dk = st.slot<orbx_kp>(kp);
+  auto dd = st.slot<uint8_t>((size_t)kp * 32);
+  auto dur = st.slot<float>(kp);
+  auto dbl = st.slot<uint8_t>(kp);
+  auto dmp = st.slot<orbm_map_point_world>(mp);
+  auto dmd = st.slot<uint8_t>((size_t)mp * 32);
+  auto dout = st.slot<int>(pp ? mp : kp);
+  auto cnt = st.slot<int>(2);  // n, nmp
+  auto dnm = st.slot<int>(1);
+  auto dpose = st.slot<orbm_pose>(1);
+  if ((rc = st.reserve()) || (rc = st.up(dk, kps, n)) || (rc = st.up(dd, desc, (size_t)n * 32)) ||
+      (rc = st.up(dur, uright, n)) || (rc = st.up(dbl, bl.data(), kp)) || (rc = st.up(dmp, mps, nmp)) ||
+      (rc = st.up(dmd, mpdesc, (size_t)nmp * 32)) || (rc = st.up(cnt, hn, 2)) || (rc = st.up(dpose, &pose, 1)) ||
+      (rc = orbm_search_by_projection_pose_batch(m, mode, dk, dd, cnt, kp, uright ? (float*)dur : nullptr, b, scale,
+                                                 nlevels, scale_factor, dbl, dpose, dmp, dmd, cnt + 1, mp, 1, th,
+                                                 dist_th, check_ori, inv_sigma2, dout, dnm, st.st)) ||
+      (rc = st.down(&nm, dnm, 1)) || (rc = st.down(out, dout, pp ? nmp : n)) || (rc = st.finish()))
+    return rc;
+  *nmatches = nm;
+  return ORBX_OK;
+}
+}  // namespace
+
+int orbm_search_by_projection_last_frame(orbm_handle m, const orbx_kp* kps, const uint8_t* desc, int n,
+                                         const float* uright, orbm_grid_bounds b, const float* scale, int nlevels,
+                                         const uint8_t* blocked, const orbm_camera* cur, const float* Tlw,
+                                         const orbm_map_point_world* mps, const uint8_t* mpdesc, int nmp, float th,
+                                         int mono, int check_ori, int* out, int* nmatches) {
+  orbm_pose pose;
+  int rc = orbm_prepare_pose(ORBM_PROJ_LAST_FRAME, cur, Tlw, mono, &pose);
+  if (rc) return rc;
+  return pose_sync(m, ORBM_PROJ_LAST_FRAME, kps, desc, n, uright, b, scale, nlevels, 1.2f, blocked, pose, mps,
+                   mpdesc, nmp, th, 100 /* TH_HIGH */, check_ori, out, nmatches);
+}
+
+int orbm_search_by_projection_keyframe(orbm_handle m, const orbx_kp* kps, const uint8_t* desc, int n,
+                                       orbm_grid_bounds b, const float* scale, int nlevels, float scale_factor,
+                                       const uint8_t* has_mp, const orbm_camera* cur,
+                                       const orbm_map_point_world* mps, const uint8_t* mpdesc, int nmp, float th,
+                                       int orb_dist, int check_ori, int* out, int* nmatches) {
+  orbm_pose pose;
+  int rc = orbm_prepare_pose(ORBM_PROJ_KEYFRAME, cur, nullptr, 0, &pose);
+  if (rc) return rc;
+  return pose_sync(m, ORBM_PROJ_KEYFRAME, kps, desc, n, nullptr, b, scale, nlevels, scale_factor, has_mp, pose,
+                   mps, mpdesc, nmp, th, orb_dist, check_ori, out, nmatches);
+}
+
+int orbm_search_by_projection_sim3(orbm_handle m, const orbx_kp* kps, const uint8_t* desc, int n,
+                                   orbm_grid_bounds b, const float* scale, int nlevels, float scale_factor,
+                                   const orbm_camera* kf, const orbm_map_point_world* mps, const uint8_t* mpdesc,
+                                   int nmp, int th, const int* matched, int* out, int* nmatches) {
+  orbm_pose pose;
+  int rc = orbm_prepare_pose(ORBM_PROJ_SIM3, kf, nullptr, 0, &pose);
+  if (rc) return rc;
+  std::vector<uint8_t> bl(std::max(n, 1), 0);
+  if (matched)
+    for (int i = 0; i < n; ++i) bl[i] = matched[i] >= 0;  // vpMatched[idx] set on entry
+  return pose_sync(m, ORBM_PROJ_SIM3, kps, desc, n, nullptr, b, scale, nlevels, scale_factor, bl.data(), pose, mps,
+                   mpdesc, nmp, (float)th, 50 /* TH_LOW */, 0, out, nmatches);
+}
+
+int orbm_fuse(orbm_handle m, const orbx_kp* kps, const uint8_t* desc, int n, const float* uright, orbm_grid_bounds b,
+              const float* scale, const float* inv_sigma2, int nlevels, float scale_factor, const orbm_camera* kf,
+              const orbm_map_point_world* mps, const uint8_t* mpdesc, int nmp, float th, int* out, int* nfused) {
+  if (!inv_sigma2) return mfail(ORBX_EINVAL, "bad argument");
+  orbm_pose pose;
+  int rc = orbm_prepare_pose(ORBM_PROJ_FUSE, kf, nullptr, 0, &pose);
+  if (rc) return rc;
+  return pose_sync(m, ORBM_PROJ_FUSE, kps, desc, n, uright, b, scale, nlevels, scale_factor, nullptr, pose, mps,
+                   mpdesc, nmp, th, 50 /* TH_LOW */, 0, out, nfused, inv_sigma2);
+}
+
+int orbm_fuse_sim3(orbm_handle m, const orbx_kp* kps, const uint8_t* desc, int n, orbm_grid_bounds b,
+                   const float* scale, int nlevels, float scale_factor, const orbm_camera* kf,
+                   const orbm_map_point_world* mps, const uint8_t* mpdesc, int nmp, float th, int* out, int* nfused) {
+  orbm_pose pose;
+  int rc = orbm_prepare_pose(ORBM_PROJ_FUSE_SIM3, kf, nullptr, 0, &pose);
+  if (rc) return rc;
+  return pose_sync(m, ORBM_PROJ_FUSE_SIM3, kps, desc, n, nullptr, b, scale, nlevels, scale_factor, nullptr, pose,
+                   mps, mpdesc, nmp, th, 50 /* TH_LOW */, 0, out, nfused);
+}
+
+int orbm_search_by_sim3(orbm_handle m, const orbx_kp* kps1, const uint8_t* desc1, int n1, orbm_grid_bounds b1,
+                        const float* T1w, const orbm_map_point_world* mps1, const uint8_t* mpdesc1,
+                        const orbx_kp* kps2, const uint8_t* desc2, int n2, orbm_grid_bounds b2, const float* T2w,
+                        const orbm_map_point_world* mps2, const uint8_t* mpdesc2, const float* scale, int nlevels,
+                        float scale_factor, const orbm_camera* cam1, float s12, const float* R12, const float* t12,
+                        float th, int* match12, int* nfound) {
+  if (!nfound || n1 < 0 || n2 < 0 || (n1 && !match12)) return mfail(ORBX_EINVAL, "bad argument");
+  orbm_pose pz[2];
+  int rc = orbm_prepare_sim3_match(cam1, T1w, T2w, s12, R12, t12, pz);
+  if (rc) return rc;
+  // direction 1: pKF1's points into pKF2 (vnMatch1); direction 2: pKF2's into pKF1 (vnMatch2)
+  std::vector<int> vn1(std::max(n1, 1), -1), vn2(std::max(n2, 1), -1);
+  int c1 = 0, c2 = 0;
+  if ((rc = pose_sync(m, ORBM_PROJ_SIM3_MATCH, kps2, desc2, n2, nullptr, b2, scale, nlevels, scale_factor, nullptr,
+                      pz[0], mps1, mpdesc1, n1, th, 100 /* TH_HIGH */, 0, vn1.data(), &c1)))
+    return rc;
+  if ((rc = pose_sync(m, ORBM_PROJ_SIM3_MATCH, kps1, desc1, n1, nullptr, b1, scale, nlevels, scale_factor, nullptr,
+                      pz[1], mps2, mpdesc2, n2, th, 100 /* TH_HIGH */, 0, vn2.data(), &c2)))
+    return rc;
+  // Check agreement (:1295-1312)
+  int nFound = 0;
+  for (int i1 = 0; i1 < n1; i1++) {
+    match12[i1] = -1;
+    const int idx2 = vn1[i1];
+    if (idx2 >= 0 && idx2 < n2 && vn2[idx2] == i1) {
+      match12[i1] = idx2;
+      nFound++;
+    }
+  }
+  *nfound = nFound;
+  return ORBX_OK;
+}
+
+int orbm_prepare_triangulation(const float* cw1, const float* T2w, const float* cam2, const float* F12,
+                               orbm_tri_pair* out) {
+  if (!cw1 || !T2w || !cam2 || !F12 || !out) return mfail(ORBX_EINVAL, "bad argument");
+  // C2 = R2w*Cw + t2w; invz = 1.0f/C2.z; ex = fx*C2.x*invz + cx (src/ORBmatcher.cc:664-670)
+  float C2[3];
+  host_rx_t(T2w, cw1, C2);
+  const float invz = 1.0f / C2[2];
+  orbm_tri_pair t{};
+  std::memcpy(t.F12, F12, sizeof t.F12);
+  t.ex = cam2[0] * C2[0] * invz + cam2[2];
+  t.ey = cam2[1] * C2[1] * invz + cam2[3];
+  *out = t;
+  return ORBX_OK;
+}
+
+int orbm_search_for_triangulation_batch(
+    orbm_handle m, const orbx_kp* d_kps1, const uint8_t* d_desc1, const float* d_uright1, const uint8_t* d_has_mp1,
+    const int* d_n1, const uint32_t* d_nodes1, const int* d_off1, const int* d_idx1, const int* d_nn1, int kp_pitch1,
+    int node_pitch1, const orbx_kp* d_kps2, const uint8_t* d_desc2, const float* d_uright2, const uint8_t* d_has_mp2,
+    const int* d_n2, const uint32_t* d_nodes2, const int* d_off2, const int* d_idx2, const int* d_nn2, int kp_pitch2,
+    int node_pitch2, const orbm_tri_pair* d_pairs, const float* scale2, const float* sigma2, int nlevels, int pairs,
+    int only_stereo, int check_ori, int* d_matches12, int out_pitch, int* d_nmatches, void* stream) {
+  if (!m || !d_kps1 || !d_desc1 || !d_uright1 || !d_has_mp1 || !d_n1 || !d_nodes1 || !d_off1 || !d_idx1 || !d_nn1 ||
+      !d_kps2 || !d_desc2 || !d_uright2 || !d_has_mp2 || !d_n2 || !d_nodes2 || !d_off2 || !d_idx2 || !d_nn2 ||
+      !d_pairs || !scale2 || !sigma2 || !d_matches12 || !d_nmatches || pairs < 1 || nlevels < 1 ||
+      nlevels > kMaxLevels || kp_pitch1 < 0 || node_pitch1 < 0 || kp_pitch2 < 1 || node_pitch2 < 1 || out_pitch < 1 ||
+      ((kp_pitch1 == 0) != (node_pitch1 == 0)))
+    return mfail(ORBX_EINVAL, "bad argument");
+  MHIP(hipSetDevice(m->device));
+  TriParams P{};
+  for (int l = 0; l < kMaxLevels; ++l) {
+    P.scale2[l] = scale2[std::min(l, nlevels - 1)];
+    P.sigma2[l] = sigma2[std::min(l, nlevels - 1)];
+  }
+  P.only_stereo = only_stereo;
+  P.check_ori = check_ori;
+  P.out_pitch = out_pitch;
+  const TriSide A{d_kps1, d_desc1, d_uright1, d_has_mp1, d_n1, d_nodes1, d_off1, d_idx1, d_nn1, kp_pitch1,
+                  node_pitch1};
+  const TriSide B{d_kps2, d_desc2, d_uright2, d_has_mp2, d_n2, d_nodes2, d_off2, d_idx2, d_nn2, kp_pitch2,
+                  node_pitch2};
+  if (launch_search_tri(P, A, B, d_pairs, pairs, d_matches12, d_nmatches, stream))
+    return mfail(ORBX_EDEVICE, "search_tri launch: %s", hipGetErrorString(hipGetLastError()));
+  return ORBX_OK;
+}
+
+int orbm_search_for_triangulation(orbm_handle m, const orbx_kp* kps1, const uint8_t* desc1, const float* uright1,
+                                  const uint8_t* has_mp1, int n1, orbm_feature_vector fv1, const orbx_kp* kps2,
+                                  const uint8_t* desc2, const float* uright2, const uint8_t* has_mp2, int n2,
+                                  orbm_feature_vector fv2, const float* cw1, const float* T2w, const float* cam2,
+                                  const float* scale2, const float* sigma2, int nlevels, const float* F12,
+                                  int only_stereo, int check_ori, int* matches12, int* nmatches) {
+  if (!m || !nmatches || n1 < 0 || n2 < 0 || fv1.n_nodes < 0 || fv2.n_nodes < 0 ||
+      (n1 && (!kps1 || !desc1 || !uright1 || !has_mp1 || !matches12)) ||
+      (n2 && (!kps2 || !desc2 || !uright2 || !has_mp2)) || (fv1.n_nodes && (!fv1.nodes || !fv1.off)) ||
+      (fv2.n_nodes && (!fv2.nodes || !fv2.off)))
+    return mfail(ORBX_EINVAL, "bad argument");
+  orbm_tri_pair tp;
+  int rc = orbm_prepare_triangulation(cw1, T2w, cam2, F12, &tp);
+  if (rc) return rc;
+  const int f1 = fv1.n_nodes ? fv1.off[fv1.n_nodes] : 0, f2 = fv2.n_nodes ? fv2.off[fv2.n_nodes] : 0;
+  if (f1 > n1 || f2 > n2) return mfail(ORBX_EINVAL, "feature vector holds more indices than keypoints");
+  for (int i = 0; i < f1; ++i)
+    if (fv1.idx[i] < 0 || fv1.idx[i] >= n1) return mfail(ORBX_EINVAL, "feature index out of range");
+  for (int i = 0; i < f2; ++i)
+    if (fv2.idx[i] < 0 || fv2.idx[i] >= n2) return mfail(ORBX_EINVAL, "feature index out of range");
+  MHIP(hipSetDevice(m->device));
+  const int k1 = std::max(n1, 1), k2 = std::max(n2, 1);
+  const int nn1 = std::max(fv1.n_nodes, 1), nn2 = std::max(fv2.n_nodes, 1);
+  const int zero = 0;  // an empty FeatureVector's off[0]
+  const int cnt[4] = {n1, fv1.n_nodes, n2, fv2.n_nodes};
+  int nm = 0;
+  Stage st(m);
+  auto dk1 = st.slot<orbx_kp>(k1), dk2 = st.slot<orbx_kp>(k2);
+  auto dd1 = st.slot<uint8_t>((size_t)k1 * 32), dd2 = st.slot<uint8_t>((size_t)k2 * 32);  // descriptors
+  auto du1 = st.slot<float>(k1), du2 = st.slot<float>(k2);                                // uRight
+  auto dm1 = st.slot<uint8_t>(k1), dm2 = st.slot<uint8_t>(k2);                            // MapPoint masks
+  auto dno1 = st.slot<uint32_t>(nn1), dno2 = st.slot<uint32_t>(nn2);                      // FeatureVector CSR
+  auto dof1 = st.slot<int>(nn1 + 1), dof2 = st.slot<int>(nn2 + 1);
+  auto dix1 = st.slot<int>(k1), dix2 = st.slot<int>(k2);
+  auto c = st.slot<int>(4);  // n1, nodes of 1, n2, nodes of 2
+  auto dtp = st.slot<orbm_tri_pair>(1);
+  auto dout = st.slot<int>(k1);
+  auto dnm = st.slot<int>(1);
+  if ((rc = st.reserve()) || (rc = st.up(dk1, kps1, n1)) || (rc = st.up(dd1, desc1, (size_t)n1 * 32)) ||
+      (rc = st.up(du1, uright1, n1)) || (rc = st.up(dm1, has_mp1, n1)) || (rc = st.up(dno1, fv1.nodes, fv1.n_nodes)) ||
+      (rc = st.up(dof1, fv1.n_nodes ? fv1.off : &zero, fv1.n_nodes + 1)) || (rc = st.up(dix1, fv1.idx, f1)) ||
+      (rc = st.up(dk2, kps2, n2)) || (rc = st.up(dd2, desc2, (size_t)n2 * 32)) || (rc = st.up(du2, uright2, n2)) ||
+      (rc = st.up(dm2, has_mp2, n2)) || (rc = st.up(dno2, fv2.nodes, fv2.n_nodes)) ||
+      (rc = st.up(dof2, fv2.n_nodes ? fv2.off : &zero, fv2.n_nodes + 1)) || (rc = st.up(dix2, fv2.idx, f2)) ||
+      (rc = st.up(c, cnt, 4)) || (rc = st.up(dtp, &tp, 1)) ||
+      (rc = orbm_search_for_triangulation_batch(m, dk1, dd1, du1, dm1, c, dno1, dof1, dix1, c + 1, k1, nn1, dk2, dd2,
+                                                du2, dm2, c + 2, dno2, dof2, dix2, c + 3, k2, nn2, dtp, scale2, sigma2,
+                                                nlevels, 1, only_stereo, check_ori, dout, k1, dnm, st.st)) ||
+      (rc = st.down(&nm, dnm, 1)) || (rc = st.down(matches12, dout, n1)) || (rc = st.finish()))
+    return rc;
+  *nmatches = nm;
+  return ORBX_OK;
+}
+
+}  // extern "C"

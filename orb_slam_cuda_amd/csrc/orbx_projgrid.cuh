@@ -14,7 +14,6 @@
 
 namespace orbx {
 
-constexpr int kGridCols = 64, kGridRows = 48;  // FRAME_GRID_COLS / ROWS  include/Frame.h:37-38
 constexpr int kGridCells = kGridCols * kGridRows;
 
 // LDS carve-up shared by the projection kernels (dynamic shared memory):

@@ -110,6 +110,92 @@ def test_search_for_triangulation_empty(pkg, O):
     assert nm == 0 and (out == -1).all()
 
 
+def test_search_for_triangulation_arena_growth_and_reuse(pkg, O):
+    """Small, large, small on one handle: the staging arena is reallocated between the calls and the
+    third call finds the large call's bytes beyond its own slots."""
+    small = triangulation_case(O, 1, W=640, H=240, nf=50, nodes=6)
+    large = triangulation_case(O, 2, nf=600, nodes=40)
+    m = pkg.ORBmatcher(0.6, True, max_kps=4096)
+    res = []
+    for c in (small, large, small):
+        out, nm = _tri_call(pkg, m, *c, False, True)
+        e, enm = O.search_for_triangulation(*c, False, True)
+        assert nm == enm and np.array_equal(out, e)
+        res.append((out, nm))
+    assert res[0][1] > 5 and res[1][1] > 50
+    assert res[0][1] == res[2][1] and np.array_equal(res[0][0], res[2][0])
+
+
+def _small_fuse(pkg, O, m, c):
+    """orbm_fuse on a case: (gpu out, gpu count, oracle out, oracle count)."""
+    from orb_slam_cuda_amd import _lib
+    sc = np.ascontiguousarray(c["scale"], np.float32)
+    isg = np.ascontiguousarray(c["inv_sigma2"], np.float32)
+    n, nmp = len(c["kps"]), len(c["mps"])
+    out = np.full(max(nmp, 1), -7, np.int32)
+    nf = C.c_int(-1)
+    cam = _cam(c["cam"])
+    _lib.check(_lib.lib().orbm_fuse(m.handle, _v(c["kps"]), _v(c["desc"]), n, _v(c["uright"]),
+                                    _lib.GridBounds(*c["bounds"]), _v(sc), _v(isg), len(sc), C.c_float(1.2),
+                                    C.byref(cam), _v(c["mps"]), _v(c["mpdesc"]), nmp, C.c_float(3.0), _v(out),
+                                    C.byref(nf)), matcher=True)
+    eout, enf = O.fuse(c["kps"], c["desc"], c["uright"], c["bounds"], c["scale"], c["inv_sigma2"], 1.2, c["cam"],
+                       c["mps"], c["mpdesc"], 3.0)
+    return out[:nmp], nf.value, eout, enf
+
+
+@pytest.mark.parametrize("stereo", [False, True])
+def test_fuse_uright_optional(pkg, O, stereo):
+    """uright null (monocular keyframe) and non-null on a 50-keypoint keyframe."""
+    c = fuse_case(O, 1, W=640, H=240, nf=50, nmp=60, stereo=stereo)
+    assert (c["uright"] is None) == (not stereo)
+    out, nf, eout, enf = _small_fuse(pkg, O, pkg.ORBmatcher(0.6, True, max_kps=4096), c)
+    assert nf == enf and np.array_equal(out, eout) and enf > 10
+
+
+def _cut(c, n, nmp):
+    """The case with its first n keypoints and first nmp map points."""
+    c = dict(c, kps=c["kps"][:n], desc=c["desc"][:n], mps=c["mps"][:nmp], mpdesc=c["mpdesc"][:nmp])
+    if c.get("uright") is not None:
+        c["uright"] = c["uright"][:n]
+    return c
+
+
+@pytest.mark.parametrize("n,nmp", [(0, 5), (7, 0)])
+def test_fuse_and_sim3_empty_sides(pkg, O, n, nmp):
+    """No keypoints against a few map points and a few keypoints against no map points, through Fuse,
+    the Sim3 Fuse and SearchBySim3 on one handle: ORBX_OK, nothing found, the oracle's output."""
+    from orb_slam_cuda_amd import _lib
+    m = pkg.ORBmatcher(0.6, True, max_kps=4096)
+    small = dict(W=640, H=240, nf=50)
+    out, nf, eout, enf = _small_fuse(pkg, O, m, _cut(fuse_case(O, 1, nmp=60, **small), n, nmp))
+    assert nf == enf == 0 and len(out) == nmp and np.array_equal(out, eout) and (out == -1).all()
+    c = _cut(sim3_case(O, 1, nmp=60, **small), n, nmp)
+    sc = np.ascontiguousarray(c["scale"], np.float32)
+    out = np.full(max(nmp, 1), -7, np.int32)
+    nf = C.c_int(-1)
+    cam = _cam(c["cam"])
+    _lib.check(_lib.lib().orbm_fuse_sim3(m.handle, _v(c["kps"]), _v(c["desc"]), n, _lib.GridBounds(*c["bounds"]),
+                                         _v(sc), len(sc), C.c_float(1.2), C.byref(cam), _v(c["mps"]),
+                                         _v(c["mpdesc"]), nmp, C.c_float(4.0), _v(out), C.byref(nf)), matcher=True)
+    eout, enf = O.fuse_sim3(c["kps"], c["desc"], c["bounds"], c["scale"], 1.2, c["cam"], c["mps"], c["mpdesc"], 4.0)
+    assert nf.value == enf == 0 and np.array_equal(out[:nmp], eout) and (out[:nmp] == -1).all()
+    # SearchBySim3: one record per keypoint, so the empty side is a keyframe without keypoints
+    kf1, kf2, cam1, s, R, t = sim3_match_case(O, 1, **small)
+    n1, n2 = (0, 7) if n == 0 else (7, 0)
+    kf1, kf2 = _cut(kf1, n1, n1), _cut(kf2, n2, n2)
+    out = np.full(max(n1, 1), -7, np.int32)
+    nf = C.c_int(-1)
+    cam = _cam(cam1)
+    _lib.check(_lib.lib().orbm_search_by_sim3(
+        m.handle, _v(kf1["kps"]), _v(kf1["desc"]), n1, _lib.GridBounds(*kf1["bounds"]), _v(kf1["Tcw"]),
+        _v(kf1["mps"]), _v(kf1["mpdesc"]), _v(kf2["kps"]), _v(kf2["desc"]), n2, _lib.GridBounds(*kf2["bounds"]),
+        _v(kf2["Tcw"]), _v(kf2["mps"]), _v(kf2["mpdesc"]), _v(sc), len(sc), C.c_float(1.2), C.byref(cam),
+        C.c_float(s), _v(R), _v(t), C.c_float(7.5), _v(out), C.byref(nf)), matcher=True)
+    e1, enf, _, _ = O.search_by_sim3(kf1, kf2, cam1, s, R, t, 7.5)
+    assert nf.value == enf == 0 and np.array_equal(out[:n1], e1) and (out[:n1] == -1).all()
+
+
 def test_search_for_triangulation_batch_shared_kf1(pkg, O):
     """One new keyframe against 6 neighbours in one launch (kp_pitch1 = node_pitch1 = 0)."""
     from orb_slam_cuda_amd import _lib

@@ -223,6 +223,94 @@ def test_search_by_bow_parity(pkg, O, kf_vs_kf, nodes, ratio, ori):
     assert nm > 5
 
 
+def _bow_scene(O, W=640, H=240, nf=300, nodes=12):
+    """Two small frames with FeatureVectors and MapPoint masks: (k1, d1, mpA, fa, k2, d2, mpB, fb)."""
+    (k1, d1), (k2, d2) = _pair(O, 50, W, H, nf)
+    rng = np.random.default_rng(nodes)
+    fa, fb = _featvec(rng, len(d1), nodes), _featvec(rng, len(d2), nodes)
+    mpA = (rng.random(len(d1)) > 0.3).astype(np.uint8)
+    mpB = (rng.random(len(d2)) > 0.3).astype(np.uint8)
+    return k1, d1, mpA, fa, k2, d2, mpB, fb
+
+
+@pytest.mark.parametrize("kf_vs_kf", [False, True])
+def test_search_by_bow_empty_sides(pkg, O, kf_vs_kf):
+    """nA = 0, nB = 0 and a FeatureVector without nodes: ORBX_OK, no match, the oracle's output."""
+    from orb_slam_cuda_amd.matcher import feature_vector_csr
+    k1, d1, mpA, fa, k2, d2, mpB, fb = _bow_scene(O)
+    m = pkg.ORBmatcher(0.7, True)
+    for (ka, da, ma, fva), (kb, db, mb, fvb) in [((k1[:0], d1[:0], mpA[:0], {}), (k2, d2, mpB, fb)),
+                                                 ((k1, d1, mpA, fa), (k2[:0], d2[:0], mpB[:0], {})),
+                                                 ((k1, d1, mpA, {}), (k2, d2, mpB, fb))]:
+        B = pkg.KeyFrame(kb, db, mb, fvb) if kf_vs_kf else pkg.Frame.from_extraction(kb, db, 640, 240, fvb)
+        out = []
+        nm = m.SearchByBoW(pkg.KeyFrame(ka, da, ma, fva), B, out)
+        rout, rnm = O.search_by_bow(da, ka["angle"], ma, feature_vector_csr(fva), db, kb["angle"],
+                                    mb if kf_vs_kf else np.ones(len(db), np.uint8), feature_vector_csr(fvb),
+                                    0.7, True, kf_vs_kf)
+        assert nm == rnm == 0 and len(out) == (len(da) if kf_vs_kf else len(db))
+        assert np.array_equal(np.array(out, np.int32), rout) and all(v == -1 for v in out)
+
+
+@pytest.mark.parametrize("kf_vs_kf", [False, True])
+def test_search_by_bow_null_mp_mask(pkg, O, kf_vs_kf):
+    """mpA null (every A feature has a MapPoint; mpB null too in KF-Frame mode): as an all-ones mask."""
+    import ctypes as C
+
+    from orb_slam_cuda_amd import _lib
+    from orb_slam_cuda_amd.matcher import _fvc, feature_vector_csr
+    k1, d1, _, fa, k2, d2, mpB, fb = _bow_scene(O)
+    ca, cb = feature_vector_csr(fa), feature_vector_csr(fb)
+    aA, aB = np.ascontiguousarray(k1["angle"]), np.ascontiguousarray(k2["angle"])
+    m = pkg.ORBmatcher(0.7, True)
+    res = np.full(len(d1) if kf_vs_kf else len(d2), -7, np.int32)
+    nm = C.c_int(-1)
+    _lib.check(_lib.lib().orbm_search_by_bow(
+        m.handle, _lib.ptr(d1), _lib.ptr(aA), None, len(d1), _fvc(ca), _lib.ptr(d2), _lib.ptr(aB),
+        _lib.ptr(mpB) if kf_vs_kf else None, len(d2), _fvc(cb), C.c_float(0.7), 1, int(kf_vs_kf), _lib.ptr(res),
+        C.byref(nm)), matcher=True)
+    rout, rnm = O.search_by_bow(d1, aA, np.ones(len(d1), np.uint8), ca, d2, aB,
+                                mpB if kf_vs_kf else np.ones(len(d2), np.uint8), cb, 0.7, True, kf_vs_kf)
+    assert nm.value == rnm and np.array_equal(res, rout) and rnm > 5
+
+
+def test_mixed_entry_points_share_one_handle(pkg, O):
+    """SearchByBoW, SearchByProjection and the stereo matches of the last extractions, interleaved
+    twice on one matcher: they share its staging arena and stream, each must equal the oracle."""
+    from orb_slam_cuda_amd.matcher import feature_vector_csr
+    from orb_slam_cuda_amd.synth import stereo_pair
+    from projcase import projection_case
+    W, H, nf = 640, 240, 300
+    k1, d1, mpA, fa, k2, d2, _, fb = _bow_scene(O, W, H, nf)
+    bow_ref = O.search_by_bow(d1, k1["angle"], mpA, feature_vector_csr(fa), d2, k2["angle"],
+                              np.ones(len(d2), np.uint8), feature_vector_csr(fb), 0.7, True, False)
+    kps, desc, ur, bounds, scale, blocked, mps, mpd = projection_case(O, 3, W=W, H=H, nf=nf, nmp=400, stereo=True)
+    proj_ref = O.search_by_projection(kps, desc, ur, bounds, scale, blocked, mps, mpd, 3.0, 0.7)
+    imL, imR = stereo_pair(5, W, H)
+    eL, eR = pkg.ORBextractor(nf, 1.2, 8, 20, 7, W, H), pkg.ORBextractor(nf, 1.2, 8, 20, 7, W, H)
+    cfg = O.config(nfeatures=nf, width=W, height=H)
+    li = O.level_info(cfg)
+    mb, mbf = 0.54, np.float32(0.54 * 718.856)
+    m = pkg.ORBmatcher(0.7, True, max_kps=4096)
+    for _ in range(2):
+        out = []
+        nm = m.SearchByBoW(pkg.KeyFrame(k1, d1, mpA, fa), pkg.Frame.from_extraction(k2, d2, W, H, fb), out)
+        assert nm == bow_ref[1] > 5 and np.array_equal(np.array(out, np.int32), bow_ref[0])
+        F = pkg.Frame(kps, desc, *bounds)
+        F.mvuRight, F.mvScaleFactors = ur, np.asarray(scale, np.float32)
+        nm = m.SearchByProjection(F, mps, mpd, 3.0, blocked=blocked)
+        assert nm == proj_ref[1] > 50 and np.array_equal(m.last_projection, proj_ref[0])
+        kL, dL = eL(imL)
+        kR, dR = eR(imR)
+        S = pkg.Frame.from_extraction(kL, dL, W, H)
+        S.mb, S.mbf = mb, float(mbf)
+        kept = pkg.ComputeStereoMatchesLast(S, eL, eR, m)
+        uR, dep, ekept = O.compute_stereo_matches(kL, dL, kR, dR, O.pyramid(cfg, imL), O.pyramid(cfg, imR),
+                                                  li["scale"], li["inv_scale"], mb, mbf)
+        assert kept == ekept > 0.3 * len(kL)
+        assert np.array_equal(S.mvuRight, uR) and np.array_equal(S.mvDepth, dep)
+
+
 def test_search_by_bow_golden(pkg, O):
     from orb_slam_cuda_amd.matcher import feature_vector_csr
     import importlib.util

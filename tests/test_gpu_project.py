@@ -78,3 +78,47 @@ def test_search_by_projection_batch(pkg, O):
         uu = u if u is not None else np.full(len(k), -1, np.float32)
         eout, enm = O.search_by_projection(k, d, uu, bounds, scale, b, p, q, 3.0, 0.8)
         assert nm[i] == enm and np.array_equal(out[i, :n[i]], eout)
+
+
+def _local_map(pkg, O, m, kps, desc, ur, bounds, scale, blocked, mps, mpd, th, ratio):
+    """One synchronous call and the oracle's answer for it: (gpu out, gpu count, oracle out, oracle count)."""
+    nm = m.SearchByProjection(_frame(pkg, kps, desc, ur, bounds, scale), mps, mpd, th, blocked=blocked)
+    eout, enm = O.search_by_projection(kps, desc, ur, bounds, scale, blocked, mps, mpd, th, ratio)
+    return m.last_projection, nm, eout, enm
+
+
+def test_search_by_projection_empty_sides(pkg, O):
+    """No keypoints against a few map points, and a few keypoints against no map points."""
+    kps, desc, ur, bounds, scale, blocked, mps, mpd = projection_case(O, 1, W=640, H=240, nf=50, nmp=60, stereo=True)
+    m = pkg.ORBmatcher(0.8, True, max_kps=4096)
+    out, nm, eout, enm = _local_map(pkg, O, m, kps[:0], desc[:0], ur[:0], bounds, scale, blocked[:0], mps[:5], mpd[:5],
+                                    3.0, 0.8)
+    assert nm == enm == 0 and len(out) == 0 and np.array_equal(out, eout)
+    out, nm, eout, enm = _local_map(pkg, O, m, kps[:7], desc[:7], ur[:7], bounds, scale, blocked[:7], mps[:0], mpd[:0],
+                                    3.0, 0.8)
+    assert nm == enm == 0 and np.array_equal(out, eout) and (out == -1).all() and len(out) == 7
+
+
+def test_search_by_projection_arena_growth_and_reuse(pkg, O):
+    """Small, large, small on one handle: the staging arena is reallocated between the calls and the
+    third call finds the large call's bytes beyond its own slots."""
+    small = projection_case(O, 1, W=640, H=240, nf=50, nmp=60, stereo=True)
+    large = projection_case(O, 2, nf=600, nmp=900, stereo=True)
+    m = pkg.ORBmatcher(0.8, True, max_kps=4096)
+    res = []
+    for c in (small, large, small):
+        out, nm, eout, enm = _local_map(pkg, O, m, *c, 3.0, 0.8)
+        assert nm == enm and np.array_equal(out, eout)
+        res.append((out.copy(), nm))
+    assert res[0][1] > 10 and res[1][1] > 100
+    assert res[0][1] == res[2][1] and np.array_equal(res[0][0], res[2][0])
+
+
+@pytest.mark.parametrize("stereo", [False, True])
+def test_search_by_projection_uright_optional(pkg, O, stereo):
+    """uright null (monocular frame) and non-null on the same 50-keypoint scene."""
+    kps, desc, ur, bounds, scale, blocked, mps, mpd = projection_case(O, 1, W=640, H=240, nf=50, nmp=60, stereo=True)
+    m = pkg.ORBmatcher(0.8, True, max_kps=4096)
+    out, nm, eout, enm = _local_map(pkg, O, m, kps, desc, ur if stereo else None, bounds, scale, blocked, mps, mpd, 3.0,
+                                    0.8)
+    assert nm == enm and np.array_equal(out, eout) and nm > 10

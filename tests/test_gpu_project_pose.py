@@ -197,3 +197,50 @@ def test_pose_batch_mixed_frames(pkg, O):
                                                       c["blocked"], c["cam"], c["Tlw"], c["mps"], c["mpdesc"], 7.0,
                                                       c["mono"])
         assert nm[i] == enm and np.array_equal(out[i, :n[i]], eout)
+
+
+def _cut(c, n, nmp, per_kp=("kps", "desc", "uright", "blocked", "has_mp", "matched")):
+    """The case with its first n keypoints and first nmp map points."""
+    c = dict(c)
+    for k in per_kp:
+        if c.get(k) is not None:
+            c[k] = c[k][:n]
+    c["mps"], c["mpdesc"] = c["mps"][:nmp], c["mpdesc"][:nmp]
+    return c
+
+
+@pytest.mark.parametrize("n,nmp", [(0, 5), (7, 0)])
+def test_pose_overloads_empty_sides(pkg, O, n, nmp):
+    """No keypoints against a few map points and a few keypoints against no map points, through the
+    last-frame, keyframe and Sim3 overloads on one handle: ORBX_OK, no match, the oracle's output."""
+    from orb_slam_cuda_amd import _lib
+    m = pkg.ORBmatcher(0.9, True, max_kps=4096)
+    small = dict(W=640, H=240, nf=50, nmp=60)
+    c = _cut(last_frame_case(O, 1, stereo=True, **small), n, nmp)
+    out, nm = gpu_last_frame(pkg, m, c, 7.0)
+    eout, enm = O.search_by_projection_last_frame(c["kps"], c["desc"], c["uright"], c["bounds"], c["scale"],
+                                                  c["blocked"], c["cam"], c["Tlw"], c["mps"], c["mpdesc"], 7.0,
+                                                  c["mono"])
+    assert nm == enm == 0 and len(out) == n and np.array_equal(out, eout) and (out == -1).all()
+
+    def call(fn, c, mid):  # mid(cam): the overload's arguments between scale_factor and out
+        sc = np.ascontiguousarray(c["scale"], np.float32)
+        out = np.full(max(n, 1), -7, np.int32)
+        nm = C.c_int(-1)
+        cam = _cam(c["cam"])
+        _lib.check(fn(m.handle, _v(c["kps"]), _v(c["desc"]), n, _lib.GridBounds(*c["bounds"]), _v(sc), len(sc),
+                      C.c_float(1.2), *mid(cam), _v(out), C.byref(nm)), matcher=True)
+        return out[:n], nm.value
+
+    c = _cut(keyframe_case(O, 1, **small), n, nmp)
+    out, nm = call(_lib.lib().orbm_search_by_projection_keyframe, c, lambda cam: (
+        _v(c["has_mp"]), C.byref(cam), _v(c["mps"]), _v(c["mpdesc"]), nmp, C.c_float(10.0), 100, 1))
+    eout, enm = O.search_by_projection_keyframe(c["kps"], c["desc"], c["bounds"], c["scale"], 1.2, c["has_mp"],
+                                                c["cam"], c["mps"], c["mpdesc"], 10.0, 100)
+    assert nm == enm == 0 and np.array_equal(out, eout) and (out == -1).all()
+    c = _cut(sim3_case(O, 1, **small), n, nmp)
+    out, nm = call(_lib.lib().orbm_search_by_projection_sim3, c, lambda cam: (
+        C.byref(cam), _v(c["mps"]), _v(c["mpdesc"]), nmp, 10, _v(c["matched"])))
+    eout, enm = O.search_by_projection_sim3(c["kps"], c["desc"], c["bounds"], c["scale"], 1.2, c["cam"], c["mps"],
+                                            c["mpdesc"], 10, c["matched"])
+    assert nm == enm == 0 and np.array_equal(out, eout) and (out == -1).all()
