@@ -270,14 +270,18 @@ int orbm_destroy(orbm_handle m);
  * (0 = ok; bit 16: orbm_hamming_top2 input over its limits, nA[p] > a_cap
  * or nB[p] > 65535, the excess rows / candidates were not searched; bit 32:
  * orbm_search_by_bow_batch saw a count above kp_pitch or a FeatureVector
- * index outside [0, n), which was skipped). SearchForInitialization keeps no
+ * index outside [0, n), which was skipped; bit 64:
+ * orbm_search_local_points_batch found more than 8192 map points in view in
+ * a frame, the points in view after the first 8192 were not searched).
+ * SearchForInitialization keeps no
  * candidate lists (8 smallest keys per query) and never sets it. Waits for
  * the matcher's own launches that may set it (on whatever streams they ran),
  * not for the device; `reset` != 0 clears it. The synchronous entry points
  * check and clear it themselves.
  *
- * Device workspaces (candidate lists, stereo SAD, pose picks, SearchByBoW row
- * records and histograms) belong to the
+ * Device workspaces (candidate lists, stereo SAD, pose picks, the compacted
+ * points in view of SearchLocalPoints, SearchByBoW row records and
+ * histograms) belong to the
  * handle: batched calls on different streams are ordered by the library
  * (each waits for the previous user of the workspace), so they never
  * overlap on it. The same holds for an extractor handle's plan buffers, and
@@ -540,6 +544,75 @@ int orbm_search_by_projection_pose_batch(
     const orbm_map_point_world* d_mps, const uint8_t* d_mpdesc, const int* d_nmp,
     int mp_pitch, int frames, float th, int dist_th, int check_ori,
     const float* inv_sigma2, int* d_out, int* d_nmatches, void* stream);
+
+/* ------------------------- Frame::isInFrustum, Tracking::SearchLocalPoints
+ * Frame::isInFrustum(pMP, viewingCosLimit) (src/Frame.cc:268-324) for every
+ * point of a local map, with the reference's float / double arithmetic
+ * operation by operation. pose: the frame's orbm_pose from
+ * orbm_prepare_pose(ORBM_PROJ_KEYFRAME, cam, NULL, 0, &pose), which holds
+ * Rt = mTcw, Ow = -Rcw^T tcw as Frame::UpdatePoseMatrices computes it, and
+ * fx, fy, cx, cy, mbf: isInFrustum needs nothing else, so it has no mode
+ * constant of its own. bounds = mnMinX/MaxX/MinY/MaxY (inclusive here);
+ * scale_factor, nlevels = mfScaleFactor, mnScaleLevels (PredictScale).
+ * Input records: pos, normal, min/max_distance, obs_positive, and valid =
+ * the point is tested at all, !isBad() && mnLastFrameSeen !=
+ * mCurrentFrame.mnId (src/Tracking.cc:1256-1259); angle and octave are
+ * ignored. Output record j: track_in_view and the mTrackProj* / view cosine /
+ * predicted level the reference leaves on the MapPoint; a point that is not
+ * valid or not in view gets an all-zero record (the reference leaves stale
+ * fields there), obs_positive apart, which is copied from the input.
+ * *n_in_view = the number of records with track_in_view. Host only: runs
+ * without a device. */
+int orbm_is_in_frustum(const orbm_pose* pose, orbm_grid_bounds bounds, float scale_factor,
+                       int nlevels, float viewing_cos_limit, const orbm_map_point_world* mps,
+                       int nmp, orbm_map_point_proj* out, int* n_in_view);
+
+/* The same on the device, asynchronous on `stream`: frame f's points at
+ * d_mps + f*mp_pitch (d_nmp[f] of them, 16-byte aligned), its pose
+ * d_poses[f], its records to d_out + f*mp_pitch (slots from d_nmp[f] on are
+ * left untouched), its count to d_n_in_view[f]. mp_pitch <= 65536. The
+ * records equal orbm_is_in_frustum's byte for byte. */
+int orbm_is_in_frustum_batch(orbm_handle m, const orbm_pose* d_poses, orbm_grid_bounds bounds,
+                             float scale_factor, int nlevels, float viewing_cos_limit,
+                             const orbm_map_point_world* d_mps, const int* d_nmp, int mp_pitch,
+                             int frames, orbm_map_point_proj* d_out, int* d_n_in_view,
+                             void* stream);
+
+/* Tracking::SearchLocalPoints' device part (src/Tracking.cc:1254-1278) in one
+ * round trip: isInFrustum on every point, then SearchByProjection(F,
+ * vpMapPoints, th) over the points in view. Frame arguments as for
+ * orbm_search_by_projection; cur = the frame's camera and pose; records as
+ * for orbm_is_in_frustum, mpdesc their descriptors. out[idx] = index into
+ * the caller's point list (all nmp of them) of the point assigned to keypoint
+ * idx, -1 where nothing was assigned. proj (nmp records, or NULL) and
+ * *n_in_view give the caller which points get IncreaseVisible() and nToMatch
+ * (:1261-1265); with nothing in view the search is skipped (:1268): out is
+ * all -1 and *nmatches 0. nmp <= 65536; the points are compacted to those in
+ * view, in order, before the search, whose limit of 8192 points therefore
+ * applies to the points in view: more gives ORBX_ECAPACITY (the message
+ * names the count; proj and *n_in_view are still filled). */
+int orbm_search_local_points(orbm_handle m, const orbx_kp* kps, const uint8_t* desc, int n,
+                             const float* uright, orbm_grid_bounds bounds, const float* scale,
+                             int nlevels, float scale_factor, const uint8_t* blocked,
+                             const orbm_camera* cur, const orbm_map_point_world* mps,
+                             const uint8_t* mpdesc, int nmp, float viewing_cos_limit, float th,
+                             float nnratio, int* out, int* nmatches, orbm_map_point_proj* proj,
+                             int* n_in_view);
+
+/* Batched device-resident variant, asynchronous on `stream`: the frame side
+ * as for orbm_search_by_projection_batch, the points as for
+ * orbm_is_in_frustum_batch with their descriptors at d_mpdesc + f*mp_pitch*32
+ * (16-byte aligned). d_proj: frames x mp_pitch records, or NULL to keep them
+ * in the handle's workspace; d_n_in_view: frames counts. A frame with more
+ * than 8192 points in view has only the first 8192 of them searched and sets
+ * status bit 64 (orbm_get_status). */
+int orbm_search_local_points_batch(
+    orbm_handle m, const orbx_kp* d_kps, const uint8_t* d_desc, const int* d_n, int kp_pitch,
+    const float* d_uright, orbm_grid_bounds bounds, const float* scale, int nlevels,
+    float scale_factor, const uint8_t* d_blocked, const orbm_pose* d_poses,
+    const orbm_map_point_world* d_mps, const uint8_t* d_mpdesc, const int* d_nmp, int mp_pitch,
+    int frames, float viewing_cos_limit, float th, float nnratio, int* d_out, int* d_nmatches,
+    orbm_map_point_proj* d_proj, int* d_n_in_view, void* stream);
 
 /* DBoW2::FeatureVector as CSR: nodes[k] ascending NodeIds; the feature
  * indices of node k are idx[off[k] .. off[k+1]). Each feature index appears

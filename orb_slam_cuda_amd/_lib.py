@@ -195,6 +195,18 @@ def lib() -> C.CDLL:
             [C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p, GridBounds, C.c_void_p, C.c_int,
                                                          C.c_float] + [C.c_void_p] * 5
             + [C.c_int, C.c_int, C.c_float, C.c_int, C.c_int] + [C.c_void_p] * 4)
+        L.orbm_is_in_frustum.argtypes = [C.POINTER(OrbmPose), GridBounds, C.c_float, C.c_int, C.c_float, C.c_void_p,
+                                         C.c_int, C.c_void_p, C.POINTER(C.c_int)]
+        L.orbm_is_in_frustum_batch.argtypes = [C.c_void_p, C.c_void_p, GridBounds, C.c_float, C.c_int, C.c_float,
+                                               C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                               C.c_void_p]
+        L.orbm_search_local_points.argtypes = (
+            PS + [C.c_void_p, GridBounds, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.POINTER(OrbmCamera),
+                  C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_void_p, C.POINTER(C.c_int),
+                  C.c_void_p, C.POINTER(C.c_int)])
+        L.orbm_search_local_points_batch.argtypes = (
+            [C.c_void_p] * 4 + [C.c_int, C.c_void_p, GridBounds, C.c_void_p, C.c_int, C.c_float] + [C.c_void_p] * 5
+            + [C.c_int, C.c_int, C.c_float, C.c_float, C.c_float] + [C.c_void_p] * 5)
         L.orbm_prepare_sim3_match.argtypes = [C.POINTER(OrbmCamera), C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
                                               C.c_void_p, C.POINTER(OrbmPose)]
         L.orbm_fuse.argtypes = (PS + [C.c_void_p, GridBounds, C.c_void_p, C.c_void_p, C.c_int, C.c_float,

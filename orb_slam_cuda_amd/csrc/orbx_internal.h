@@ -313,6 +313,25 @@ int launch_search_pose(const PoseParams& P, const orbx_kp* kps, const uint8_t* d
                        const float* uright, const uint8_t* blocked, const orbm_pose* poses,
                        const orbm_map_point_world* mps, const uint8_t* mpdesc, const int* nmp, int frames, int* picks,
                        int* out, int* nmatches, void* stream);
+// orbx_frustum.hip — Frame::isInFrustum per point, the stable compaction of the
+// points in view and the index map back (Tracking::SearchLocalPoints)
+struct FrustumParams {
+  float minX, maxX, minY, maxY;  // mnMinX .. mnMaxY
+  float pred_thr[kMaxLevels];    // PredictScale thresholds (orbm_predict_scale_thresholds)
+  int L;                         // mnScaleLevels
+  float cos_limit;               // viewingCosLimit
+  int mp_pitch;
+};
+constexpr int kFrustumMaxView = 8192;  // points in view search_proj_kernel takes per frame (its kProjMaxMp)
+constexpr int kStatusViewOverflow = 64;  // matcher status bit: more than kFrustumMaxView points in view
+int launch_frustum(const FrustumParams& P, const orbm_pose* poses, const orbm_map_point_world* mps, const int* nmp,
+                   int frames, orbm_map_point_proj* out, int* n_in_view, void* stream);
+// c_*: per frame c_pitch compacted records, descriptors and original indices, c_nmp[f] of them
+// (<= kFrustumMaxView); err: the status word for kStatusViewOverflow, or null
+int launch_compact_in_view(const orbm_map_point_proj* proj, const uint8_t* mpdesc, const int* nmp, int mp_pitch,
+                           int frames, orbm_map_point_proj* c_proj, uint8_t* c_desc, int* c_map, int* c_nmp,
+                           int c_pitch, int* err, void* stream);
+int launch_remap_out(int* out, const int* n, int kp_pitch, const int* c_map, int c_pitch, int frames, void* stream);
 // orbx_triangulate.hip — SearchForTriangulation, one keyframe pair per workgroup
 struct TriSide {  // one side of the pairs; pitches of 0 share one keyframe across pairs
   const orbx_kp* kps;

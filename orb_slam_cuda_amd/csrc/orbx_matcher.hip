@@ -2,7 +2,8 @@
 // its workspaces, the batch (device-array) entry points and the synchronous
 // host-array entry points staged through the handle's arena. The kernels are in
 // orbx_top2.hip, orbx_bow.hip, orbx_init.hip, orbx_stereo.hip,
-// orbx_project.hip, orbx_project_pose.hip and orbx_triangulate.hip.
+// orbx_project.hip, orbx_project_pose.hip, orbx_frustum.hip and
+// orbx_triangulate.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -18,6 +19,7 @@
 #include <vector>
 
 #include "orbx_internal.h"
+#include "orbx_posemath.cuh"
 
 using namespace orbx;
 
@@ -56,9 +58,11 @@ struct orbx_matcher {
   bool bow_clean = false;     // bow_hist / bow_rec hold their between-calls values
   int* pose_picks = nullptr;  // pose-projection picks per point (frames x mp_pitch)
   size_t pose_picks_cap = 0;
+  uint8_t* view_ws = nullptr;  // SearchLocalPoints: isInFrustum records, then the points in view compacted
+  size_t view_ws_bytes = 0;
   hipStream_t stream = nullptr;
-  WsOrder ws;  // stream order of cand / stereo_sad / pose_picks / bow_* across caller streams
-  StreamMarks errm;  // streams of the launches that may set `err` (top-2, SearchByBoW)
+  WsOrder ws;  // stream order of cand / stereo_sad / pose_picks / view_ws / bow_* across caller streams
+  StreamMarks errm;  // streams of the launches that may set `err` (top-2, SearchByBoW, SearchLocalPoints)
   // staging for the synchronous entry points
   void* stage = nullptr;
   size_t stage_bytes = 0;
@@ -232,6 +236,7 @@ int orbm_destroy(orbm_handle m) {
   if (m->bow_hist) (void)hipFree(m->bow_hist);
   if (m->bow_rec) (void)hipFree(m->bow_rec);
   if (m->pose_picks) (void)hipFree(m->pose_picks);
+  if (m->view_ws) (void)hipFree(m->view_ws);
   if (m->stage) (void)hipFree(m->stage);
   if (m->h_stage) (void)hipHostFree(m->h_stage);
   if (m->stream) (void)hipStreamDestroy(m->stream);
@@ -808,6 +813,184 @@ int orbm_search_by_projection(orbm_handle m, const orbx_kp* kps, const uint8_t* 
                                             dmp, dmd, cnt + 1, mp, 1, th, nnratio, dout, dnm, st.st)) ||
       (rc = st.down(&nm, dnm, 1)) || (rc = st.down(out, dout, n)) || (rc = st.finish()))
     return rc;
+  *nmatches = nm;
+  return ORBX_OK;
+}
+
+// ------------------------------- Frame::isInFrustum, Tracking::SearchLocalPoints
+static int frustum_params(orbm_grid_bounds b, float scale_factor, int nlevels, float viewing_cos_limit, int mp_pitch,
+                          FrustumParams* P) {
+  if (nlevels < 1 || nlevels > kMaxLevels) return mfail(ORBX_EINVAL, "nlevels must be in 1..%d", kMaxLevels);
+  if (!(b.max_x > b.min_x) || !(b.max_y > b.min_y)) return mfail(ORBX_EINVAL, "empty grid bounds");
+  *P = FrustumParams{};
+  P->minX = b.min_x;
+  P->maxX = b.max_x;
+  P->minY = b.min_y;
+  P->maxY = b.max_y;
+  // the thresholds of the thread's last (scale factor, levels) are kept: the
+  // shim's Frame::isInFrustum comes here once per point
+  struct Thr {
+    float sf = 0.f;
+    int L = 0;
+    float thr[kMaxLevels];
+  };
+  static thread_local Thr last;
+  if (last.L != nlevels || last.sf != scale_factor) {
+    last.L = 0;
+    const int rc = orbm_predict_scale_thresholds(scale_factor, nlevels, last.thr);
+    if (rc) return rc;
+    last.sf = scale_factor;
+    last.L = nlevels;
+  }
+  std::memcpy(P->pred_thr, last.thr, sizeof last.thr);
+  P->L = nlevels;
+  P->cos_limit = viewing_cos_limit;
+  P->mp_pitch = mp_pitch;
+  return ORBX_OK;
+}
+
+int orbm_is_in_frustum(const orbm_pose* pose, orbm_grid_bounds b, float scale_factor, int nlevels,
+                       float viewing_cos_limit, const orbm_map_point_world* mps, int nmp, orbm_map_point_proj* out,
+                       int* n_in_view) {
+  if (!pose || !n_in_view || nmp < 0 || (nmp && (!mps || !out))) return mfail(ORBX_EINVAL, "bad argument");
+  FrustumParams P;
+  const int rc = frustum_params(b, scale_factor, nlevels, viewing_cos_limit, std::max(nmp, 1), &P);
+  if (rc) return rc;
+  int c = 0;
+  for (int j = 0; j < nmp; ++j) c += frustum_point(P, *pose, mps[j], &out[j]) ? 1 : 0;
+  *n_in_view = c;
+  return ORBX_OK;
+}
+
+int orbm_is_in_frustum_batch(orbm_handle m, const orbm_pose* d_poses, orbm_grid_bounds b, float scale_factor,
+                             int nlevels, float viewing_cos_limit, const orbm_map_point_world* d_mps,
+                             const int* d_nmp, int mp_pitch, int frames, orbm_map_point_proj* d_out,
+                             int* d_n_in_view, void* stream) {
+  if (!m || !d_poses || !d_mps || !d_nmp || !d_out || !d_n_in_view || frames < 1 || mp_pitch < 1)
+    return mfail(ORBX_EINVAL, "bad argument");
+  if (mp_pitch > 65536) return mfail(ORBX_ECAPACITY, "more than 65536 map points per frame");
+  FrustumParams P;
+  const int rc = frustum_params(b, scale_factor, nlevels, viewing_cos_limit, mp_pitch, &P);
+  if (rc) return rc;
+  MHIP(hipSetDevice(m->device));
+  MHIP(hipMemsetAsync(d_n_in_view, 0, (size_t)frames * 4, (hipStream_t)stream));
+  if (launch_frustum(P, d_poses, d_mps, d_nmp, frames, d_out, d_n_in_view, stream))
+    return mfail(ORBX_EDEVICE, "frustum launch: %s", hipGetErrorString(hipGetLastError()));
+  return ORBX_OK;
+}
+
+// status: the compaction reports more than kFrustumMaxView points in view in
+// the handle's status word (the batch call); the synchronous call reads the
+// count itself instead
+static int local_points_batch(orbm_handle m, const orbx_kp* d_kps, const uint8_t* d_desc, const int* d_n, int kp_pitch,
+                              const float* d_uright, orbm_grid_bounds b, const float* scale, int nlevels,
+                              float scale_factor, const uint8_t* d_blocked, const orbm_pose* d_poses,
+                              const orbm_map_point_world* d_mps, const uint8_t* d_mpdesc, const int* d_nmp,
+                              int mp_pitch, int frames, float viewing_cos_limit, float th, float nnratio, int* d_out,
+                              int* d_nmatches, orbm_map_point_proj* d_proj, int* d_n_in_view, void* stream,
+                              bool status) {
+  if (!m || !d_kps || !d_desc || !d_n || !scale || !d_blocked || !d_poses || !d_mps || !d_mpdesc || !d_nmp ||
+      !d_out || !d_nmatches || !d_n_in_view || frames < 1 || kp_pitch < 1 || mp_pitch < 1)
+    return mfail(ORBX_EINVAL, "bad argument");
+  if (mp_pitch > 65536) return mfail(ORBX_ECAPACITY, "more than 65536 map points per frame");
+  if (proj_lds_bytes(kp_pitch) > 156 * 1024) return mfail(ORBX_ECAPACITY, "kp_pitch %d too large", kp_pitch);
+  FrustumParams P;
+  int rc = frustum_params(b, scale_factor, nlevels, viewing_cos_limit, mp_pitch, &P);
+  if (rc) return rc;
+  MHIP(hipSetDevice(m->device));
+  hipStream_t s = (hipStream_t)stream;
+  // scratch: the isInFrustum records (when the caller keeps none), then per
+  // frame the points in view: records, descriptors, original indices, count
+  const int cp = std::min(mp_pitch, kFrustumMaxView);
+  auto a256 = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t o_cproj = d_proj ? 0 : a256((size_t)frames * mp_pitch * sizeof(orbm_map_point_proj));
+  const size_t o_cdesc = o_cproj + a256((size_t)frames * cp * sizeof(orbm_map_point_proj));
+  const size_t o_cmap = o_cdesc + a256((size_t)frames * cp * 32);
+  const size_t o_cnmp = o_cmap + a256((size_t)frames * cp * 4);
+  const size_t need = o_cnmp + a256((size_t)frames * 4);
+  if (m->ws.before(s)) return mfail(ORBX_EDEVICE, "stream wait on the workspace failed");
+  if (m->view_ws_bytes < need) {
+    if (m->ws.ev) MHIP(hipEventSynchronize(m->ws.ev));
+    if (m->view_ws) MHIP(hipFree(m->view_ws));
+    m->view_ws = nullptr;
+    m->view_ws_bytes = 0;
+    if (hipMalloc(&m->view_ws, need) != hipSuccess) return mfail(ORBX_ENOMEM, "local points workspace");
+    m->view_ws_bytes = need;
+  }
+  orbm_map_point_proj* proj = d_proj ? d_proj : (orbm_map_point_proj*)m->view_ws;
+  orbm_map_point_proj* c_proj = (orbm_map_point_proj*)(m->view_ws + o_cproj);
+  uint8_t* c_desc = m->view_ws + o_cdesc;
+  int* c_map = (int*)(m->view_ws + o_cmap);
+  int* c_nmp = (int*)(m->view_ws + o_cnmp);
+  MHIP(hipMemsetAsync(d_n_in_view, 0, (size_t)frames * 4, s));
+  if (launch_frustum(P, d_poses, d_mps, d_nmp, frames, proj, d_n_in_view, stream) ||
+      launch_compact_in_view(proj, d_mpdesc, d_nmp, mp_pitch, frames, c_proj, c_desc, c_map, c_nmp, cp,
+                             status ? m->err : nullptr, stream))
+    return mfail(ORBX_EDEVICE, "local points launch: %s", hipGetErrorString(hipGetLastError()));
+  // a frame with nothing in view (src/Tracking.cc:1268 skips the search) leaves out = -1, nmatches = 0
+  if ((rc = orbm_search_by_projection_batch(m, d_kps, d_desc, d_n, kp_pitch, d_uright, b, scale, nlevels, d_blocked,
+                                            c_proj, c_desc, c_nmp, cp, frames, th, nnratio, d_out, d_nmatches,
+                                            stream)))
+    return rc;
+  if (launch_remap_out(d_out, d_n, kp_pitch, c_map, cp, frames, stream))
+    return mfail(ORBX_EDEVICE, "local points launch: %s", hipGetErrorString(hipGetLastError()));
+  if (m->ws.after(s) || (status && m->errm.mark(s))) return mfail(ORBX_EDEVICE, "event record failed");
+  return ORBX_OK;
+}
+
+int orbm_search_local_points_batch(orbm_handle m, const orbx_kp* d_kps, const uint8_t* d_desc, const int* d_n,
+                                   int kp_pitch, const float* d_uright, orbm_grid_bounds b, const float* scale,
+                                   int nlevels, float scale_factor, const uint8_t* d_blocked,
+                                   const orbm_pose* d_poses, const orbm_map_point_world* d_mps,
+                                   const uint8_t* d_mpdesc, const int* d_nmp, int mp_pitch, int frames,
+                                   float viewing_cos_limit, float th, float nnratio, int* d_out, int* d_nmatches,
+                                   orbm_map_point_proj* d_proj, int* d_n_in_view, void* stream) {
+  return local_points_batch(m, d_kps, d_desc, d_n, kp_pitch, d_uright, b, scale, nlevels, scale_factor, d_blocked,
+                            d_poses, d_mps, d_mpdesc, d_nmp, mp_pitch, frames, viewing_cos_limit, th, nnratio, d_out,
+                            d_nmatches, d_proj, d_n_in_view, stream, true);
+}
+
+int orbm_search_local_points(orbm_handle m, const orbx_kp* kps, const uint8_t* desc, int n, const float* uright,
+                             orbm_grid_bounds b, const float* scale, int nlevels, float scale_factor,
+                             const uint8_t* blocked, const orbm_camera* cur, const orbm_map_point_world* mps,
+                             const uint8_t* mpdesc, int nmp, float viewing_cos_limit, float th, float nnratio,
+                             int* out, int* nmatches, orbm_map_point_proj* proj, int* n_in_view) {
+  if (!m || !nmatches || !n_in_view || !cur || !scale || n < 0 || nmp < 0 ||
+      (n && (!kps || !desc || !blocked || !out)) || (nmp && (!mps || !mpdesc)))
+    return mfail(ORBX_EINVAL, "bad argument");
+  if (nmp > 65536) return mfail(ORBX_ECAPACITY, "more than 65536 map points");
+  orbm_pose pose;
+  int rc = orbm_prepare_pose(ORBM_PROJ_KEYFRAME, cur, nullptr, 0, &pose);
+  if (rc) return rc;
+  MHIP(hipSetDevice(m->device));
+  const int kp = std::max(n, 1), mp = std::max(nmp, 1);
+  const int hn[2] = {n, nmp};
+  int nm = 0, niv = 0;
+  Stage st(m);
+  auto dk = st.slot<orbx_kp>(kp);
+  auto dd = st.slot<uint8_t>((size_t)kp * 32);
+  auto dur = st.slot<float>(kp);
+  auto dbl = st.slot<uint8_t>(kp);
+  auto dmp = st.slot<orbm_map_point_world>(mp);
+  auto dmd = st.slot<uint8_t>((size_t)mp * 32);
+  auto dpr = st.slot<orbm_map_point_proj>(mp);
+  auto dout = st.slot<int>(kp);
+  auto cnt = st.slot<int>(2);  // n, nmp
+  auto dnm = st.slot<int>(1);
+  auto dniv = st.slot<int>(1);
+  auto dpose = st.slot<orbm_pose>(1);
+  if ((rc = st.reserve()) || (rc = st.up(dk, kps, n)) || (rc = st.up(dd, desc, (size_t)n * 32)) ||
+      (rc = st.up(dur, uright, n)) || (rc = st.up(dbl, blocked, n)) || (rc = st.up(dmp, mps, nmp)) ||
+      (rc = st.up(dmd, mpdesc, (size_t)nmp * 32)) || (rc = st.up(cnt, hn, 2)) || (rc = st.up(dpose, &pose, 1)) ||
+      (rc = local_points_batch(m, dk, dd, cnt, kp, uright ? (float*)dur : nullptr, b, scale, nlevels, scale_factor,
+                               dbl, dpose, dmp, dmd, cnt + 1, mp, 1, viewing_cos_limit, th, nnratio, dout, dnm, dpr,
+                               dniv, st.st, false)) ||
+      (rc = st.down(&nm, dnm, 1)) || (rc = st.down(&niv, dniv, 1)) || (rc = st.down(out, dout, n)) ||
+      (proj && (rc = st.down(proj, dpr, nmp))) || (rc = st.finish()))
+    return rc;
+  *n_in_view = niv;
+  if (niv > kFrustumMaxView)
+    return mfail(ORBX_ECAPACITY, "%d map points in view, more than %d can be searched", niv, kFrustumMaxView);
   *nmatches = nm;
   return ORBX_OK;
 }

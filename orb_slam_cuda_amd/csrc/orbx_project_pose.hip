@@ -30,6 +30,7 @@
 // One 1024-thread workgroup per frame; the keypoint grid lives in LDS
 // (orbx_projgrid.cuh); picks are kept per point in a global scratch array so
 // the number of points per frame is not bounded by registers.
+#include "orbx_posemath.cuh"
 #include "orbx_projgrid.cuh"
 
 namespace orbx {
@@ -38,30 +39,6 @@ constexpr int kPoseThreads = 1024;
 constexpr int kHisto = 30;  // ORBmatcher::HISTO_LENGTH
 
 size_t pose_lds_bytes(int kp_pitch) { return proj_grid_lds_bytes(kp_pitch); }
-
-// R*x + t, row r of the 3x4 T: gemm's small-matrix path (float dot products,
-// then (float)(t*1.0 + c*1.0) in double)
-__device__ inline float pose_row(const float* T, int r, float x, float y, float z) {
-  const float t = __fadd_rn(__fadd_rn(__fmul_rn(T[4 * r], x), __fmul_rn(T[4 * r + 1], y)), __fmul_rn(T[4 * r + 2], z));
-  return __double2float_rn(__dadd_rn((double)t, (double)T[4 * r + 3]));
-}
-
-// cv::norm (NORM_L2) of 3 floats: sqrt of the double sum of squares
-__device__ inline float norm3(float a, float b, float c) {
-  const double s = __dadd_rn(__dadd_rn(__dmul_rn((double)a, (double)a), __dmul_rn((double)b, (double)b)),
-                             __dmul_rn((double)c, (double)c));
-  return __double2float_rn(__dsqrt_rn(s));
-}
-
-// MapPoint::PredictScale (src/MapPoint.cc:390-422) from the host's thresholds
-__device__ inline int predict_level(const PoseParams& P, float maxd, float dist) {
-  const float ratio = __fdiv_rn(maxd, dist);
-  if (__builtin_isinf(ratio)) return 0;  // ceil(log(inf)) -> int: INT_MIN on x86, clamped to 0
-  int l = 0;
-#pragma unroll
-  for (int k = 0; k < kMaxLevels - 1; ++k) l += (k < P.L - 1 && ratio >= P.pred_thr[k]) ? 1 : 0;
-  return l;
-}
 
 struct PoseQuery {
   float u, v, rad, ur;  // window centre and radius; ur: right-image coordinate (LAST_FRAME stereo)

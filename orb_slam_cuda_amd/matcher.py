@@ -7,6 +7,8 @@ Mirrors include/ORBmatcher.h:37-102 for the hot-path searches:
     nmatches = m.SearchByBoW(pKF, F, vpMapPointMatches)          # KF - Frame
     nmatches = m.SearchByBoW(pKF1, pKF2, vpMatches12)            # KF - KF
     nmatches = m.SearchByProjection(F, mps, mp_desc, th)         # local map (Frame::isInFrustum records)
+    nmatches, in_view = m.SearchLocalPoints(F, vpLocalMapPoints, th)  # isInFrustum + the local-map search
+    records = F.isInFrustum(vpLocalMapPoints, viewingCosLimit)    # Frame::isInFrustum (host)
     nmatches = m.SearchByProjection(CurrentFrame, LastFrame, th, bMono)
     nmatches = m.SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist)
     nmatches = m.SearchByProjection(pKF, Scw, vpPoints, vpMatched, th)
@@ -124,6 +126,21 @@ class Frame:
     @property
     def mvKeys(self) -> np.ndarray:
         return self.mvKeysUn
+
+    def isInFrustum(self, mps_idx, viewingCosLimit: float = 0.5) -> np.ndarray:
+        """Frame::isInFrustum (src/Frame.cc:268-324) for the MapPoints mps_idx (rows of self.mpMap, -1 =
+        NULL; a bad point is not tested), on the host: MAP_POINT_PROJ_DTYPE records, track_in_view set
+        for the points in view, zeros for the others."""
+        rec, _ = self.mpMap.records(mps_idx, None, None, ~self.mpMap.bad_of(mps_idx))
+        pose = _lib.OrbmPose()
+        cam = camera(self.fx, self.fy, self.cx, self.cy, self.mb, self.mbf, self.mTcw)
+        check(lib().orbm_prepare_pose(_lib.ORBM_PROJ_KEYFRAME, C.byref(cam), None, 0, C.byref(pose)), matcher=True)
+        out = np.zeros(len(rec), MAP_POINT_PROJ_DTYPE)
+        niv = C.c_int(0)
+        check(lib().orbm_is_in_frustum(C.byref(pose), _grid(self), C.c_float(self.mfScaleFactor),
+                                       len(self.mvScaleFactors), C.c_float(viewingCosLimit), ptr(rec), len(rec),
+                                       ptr(out), C.byref(niv)), matcher=True)
+        return out
 
     @classmethod
     def from_extraction(cls, kps, desc, width, height, featvec=None):
@@ -569,6 +586,43 @@ class ORBmatcher:
         F.mvpMapPoints[hit] = out[:n][hit]
         self.last_projection = out[:n].copy()
         return nm.value
+
+    def SearchLocalPoints(self, F: Frame, vpLocalMapPoints, th: float, viewingCosLimit: float = 0.5,
+                          seen=None):
+        """Tracking::SearchLocalPoints' matcher part (src/Tracking.cc:1254-1278): Frame::isInFrustum on
+        every point of vpLocalMapPoints (rows of F.mpMap), then SearchByProjection(F, vpLocalMapPoints,
+        th) over the points in view, in one device round trip. seen[i]: the point was already matched in
+        this frame (mnLastFrameSeen == mCurrentFrame.mnId) and is not tested, like a bad one. Keypoints
+        holding a map point are blocked as in SearchByProjection(F, records, descriptors, th); assigned
+        keypoints get the point in F.mvpMapPoints. Returns (nmatches, in_view_mask); the isInFrustum
+        records stay in self.last_frustum."""
+        mp = F.mpMap
+        pts = np.asarray(vpLocalMapPoints, np.int64)
+        kps = np.ascontiguousarray(F.mvKeysUn, KP_DTYPE)
+        d = np.ascontiguousarray(F.mDescriptors, np.uint8)
+        n = len(kps)
+        if F.mvpMapPoints is None:
+            F.mvpMapPoints = np.full(n, -1, np.int32)
+        valid = ~mp.bad_of(pts)
+        if seen is not None:
+            valid &= ~np.asarray(seen, bool)
+        rec, md = mp.records(pts, None, None, valid)
+        bl = np.ascontiguousarray(F.mvpMapPoints >= 0, np.uint8)
+        ur = None if F.mvuRight is None else np.ascontiguousarray(F.mvuRight, np.float32)
+        sc = np.ascontiguousarray(F.mvScaleFactors, np.float32)
+        cam = camera(F.fx, F.fy, F.cx, F.cy, F.mb, F.mbf, F.mTcw)
+        out = np.full(max(n, 1), -1, np.int32)
+        proj = np.zeros(len(rec), MAP_POINT_PROJ_DTYPE)
+        nm, niv = C.c_int(0), C.c_int(0)
+        check(lib().orbm_search_local_points(
+            self._h, ptr(kps), ptr(d), n, ptr(ur), _grid(F), ptr(sc), len(sc), C.c_float(F.mfScaleFactor), ptr(bl),
+            C.byref(cam), ptr(rec), ptr(md), len(rec), C.c_float(viewingCosLimit), C.c_float(th),
+            C.c_float(self.mfNNratio), ptr(out), C.byref(nm), ptr(proj), C.byref(niv)), matcher=True)
+        o = out[:n]
+        F.mvpMapPoints[o >= 0] = pts[o[o >= 0]]
+        self.last_projection = o.copy()
+        self.last_frustum = proj
+        return nm.value, proj["track_in_view"] != 0
 
     def SearchByBoW(self, A: KeyFrame, B, out: list | None = None) -> int:
         """KF-Frame (B is a Frame) or KF-KF (B is a KeyFrame). Fills `out` with matched

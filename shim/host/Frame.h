@@ -5,7 +5,8 @@
 // mDescriptorsRight, mvuRight, mvDepth), the pose mTcw, mvpMapPoints,
 // mvbOutlier, the scale tables and the static image bounds mnMinX..mnMaxY
 // (Frame.h:110-186). ComputeBoW is src/Frame.cc:394-401; ComputeStereoMatches
-// (:465-639) is the drop-in body in shim/src/Frame.cc. A test stand-in; a
+// (:465-639) and isInFrustum (:268-324) are the drop-in bodies in
+// shim/src/Frame.cc. A test stand-in; a
 // real build uses the reference's Frame with that one body replaced.
 #ifndef ORBX_SHIM_FRAME_H
 #define ORBX_SHIM_FRAME_H
@@ -98,6 +99,12 @@ class Frame {
   // (src/Frame.cc:77-89) in one call (shim/src/Frame.cc): mvKeys, mDescriptors,
   // mvKeysRight, mDescriptorsRight, N, mvuRight, mvDepth
   void ExtractStereo(const cv::Mat& imLeft, const cv::Mat& imRight);
+  // Check if a MapPoint is in the frustum of the camera and fill the variables
+  // of the MapPoint used by the tracking (src/Frame.cc:268-324; shim/src/Frame.cc,
+  // over orbm_is_in_frustum on the host). Tracking::SearchLocalPoints' loop over
+  // it compiles as written; ORBmatcher::SearchLocalPoints does the loop and the
+  // search that follows in one device call.
+  bool isInFrustum(MapPoint* pMP, float viewingCosLimit);
 
   ORBVocabulary* mpORBvocabulary = nullptr;
   ORBextractor* mpORBextractorLeft = nullptr;
@@ -105,6 +112,7 @@ class Frame {
   static float fx, fy, cx, cy, invfx, invfy;
   float mbf = 0.f, mb = 0.f;
   int N = 0;
+  long unsigned int mnId = 0;
   std::vector<cv::KeyPoint> mvKeys, mvKeysRight, mvKeysUn;
   std::vector<float> mvuRight, mvDepth;
   DBoW2::BowVector mBowVec;

@@ -3,7 +3,9 @@
 // GetDescriptor, Get{Min,Max}DistanceInvariance, Observations(), isBad(),
 // IsInKeyFrame/GetIndexInKeyFrame, AddObservation, Replace and
 // ComputeDistinctiveDescriptors (src/MapPoint.cc:80-370), and the tracking
-// fields Frame::isInFrustum leaves (mTrackProj*, mbTrackInView, ...). A test
+// fields Frame::isInFrustum leaves (mTrackProj*, mbTrackInView, ...) with the
+// bookkeeping Tracking::SearchLocalPoints does around it (mnLastFrameSeen,
+// IncreaseVisible). A test
 // stand-in with the reference's names; a real build uses the reference's
 // MapPoint. Locks and the Map are omitted (one thread, no map).
 #ifndef ORBX_SHIM_MAPPOINT_H
@@ -54,6 +56,9 @@ class MapPoint {
   bool mbTrackInView = false;
   int mnTrackScaleLevel = 0;
   float mTrackViewCos = 0.f;
+  long unsigned int mnLastFrameSeen = 0;
+  void IncreaseVisible(int n = 1) { mnVisible += n; }  // MapPoint.cc:229-233
+  int mnVisible = 1;
   // test scene setters
   cv::Mat mWorldPos, mNormalVector, mDescriptor;
   void SetScaleDistances(float minDistance, float maxDistance) {
@@ -64,6 +69,7 @@ class MapPoint {
 
  protected:
   friend class ORBmatcher;  // the one-line addition a real build makes to include/MapPoint.h
+  friend class Frame;       // and this one, for the drop-in Frame::isInFrustum
   float mfMinDistance = 0.f, mfMaxDistance = 0.f;
 
  private:

@@ -12,6 +12,7 @@
 //   op 7 SearchBySim3(pKF1, pKF2, vpMatches12, ...)        LoopClosing.cc:362
 //   op 8 SearchForTriangulation(pKF1, pKF2, F12, ...)      LocalMapping.cc:301
 //   op 9 SearchByBoW(pKF, F, vpMapPointMatches)            Tracking.cc:842, 1465
+//   op 10 Tracking::SearchLocalPoints' body                Tracking.cc:1229-1279
 // --scene-latency: the same scene rebuilt per call, only the method call on
 // the host clock (median / p99 over the calls after the warm ones).
 // Scene file: records of [u32 name length][name][u32 dtype 0 u8 / 1 i32 /
@@ -242,6 +243,67 @@ void write_ints(const std::string& path, const std::vector<int>& v) {
 }
 }  // namespace
 
+// Tracking::SearchLocalPoints (src/Tracking.cc:1229-1279) on a frame and a
+// local map, th given by the scene. one_call = false: the reference's body as
+// written, Frame::isInFrustum per point and then SearchByProjection; true: the
+// same bookkeeping around one ORBmatcher::SearchLocalPoints call.
+// -> [nToMatch, n, F.mvpMapPoints..., per local point: mbTrackInView, mnVisible]
+static void search_local_points(const Scene& s, bool one_call, std::vector<int>& res) {
+  auto pool = map_points(s);
+  auto F = frame(s, "A", pool);
+  Frame& mCurrentFrame = *F;
+  mCurrentFrame.mnId = 7;
+  set_nobs(s, pool);
+  std::vector<MapPoint*> mvpLocalMapPoints = pointers(s, "vp", pool);
+  if (s.has("mp_seen")) {  // matched earlier in this frame (TrackWithMotionModel / TrackReferenceKeyFrame)
+    const auto seen = s.vec<uint8_t>("mp_seen");
+    for (size_t i = 0; i < pool.size(); ++i)
+      if (seen[i]) pool[i]->mnLastFrameSeen = mCurrentFrame.mnId;
+  }
+  const float th = s.f("th");
+  // Do not search map points already matched
+  for (std::vector<MapPoint*>::iterator vit = mCurrentFrame.mvpMapPoints.begin(),
+                                       vend = mCurrentFrame.mvpMapPoints.end();
+       vit != vend; vit++) {
+    MapPoint* pMP = *vit;
+    if (pMP) {
+      if (pMP->isBad()) {
+        *vit = static_cast<MapPoint*>(NULL);
+      } else {
+        pMP->IncreaseVisible();
+        pMP->mnLastFrameSeen = mCurrentFrame.mnId;
+        pMP->mbTrackInView = false;
+      }
+    }
+  }
+  int nToMatch = 0, n = 0;
+  ORBmatcher matcher(s.f("nnratio"));
+  if (one_call) {
+    n = matcher.SearchLocalPoints(mCurrentFrame, mvpLocalMapPoints, th, &nToMatch, 0.5f);
+  } else {
+    // Project points in frame and check its visibility
+    for (std::vector<MapPoint*>::iterator vit = mvpLocalMapPoints.begin(), vend = mvpLocalMapPoints.end(); vit != vend;
+         vit++) {
+      MapPoint* pMP = *vit;
+      if (pMP->mnLastFrameSeen == mCurrentFrame.mnId) continue;
+      if (pMP->isBad()) continue;
+      // Project (this fills MapPoint variables for matching)
+      if (mCurrentFrame.isInFrustum(pMP, 0.5)) {
+        pMP->IncreaseVisible();
+        nToMatch++;
+      }
+    }
+    if (nToMatch > 0) n = matcher.SearchByProjection(mCurrentFrame, mvpLocalMapPoints, th);
+  }
+  res.push_back(nToMatch);
+  res.push_back(n);
+  for (MapPoint* p : mCurrentFrame.mvpMapPoints) res.push_back(id_of(p));
+  for (MapPoint* p : mvpLocalMapPoints) {
+    res.push_back(p->mbTrackInView ? 1 : 0);
+    res.push_back(p->mnVisible);
+  }
+}
+
 // One method call on the scene's state (built here), its results as int32
 // arrays (see each op) and its host time in *ms (the call alone).
 static void run_op(const Scene& s, std::vector<int>& res, double* ms) {
@@ -375,6 +437,13 @@ static void run_op(const Scene& s, std::vector<int>& res, double* ms) {
       toc();
       res.push_back(n);
       for (MapPoint* p : matches) res.push_back(id_of(p));
+      break;
+    }
+    case 10: {  // -> the reference's body, then the one-call body, each as search_local_points writes it
+      tic();
+      search_local_points(s, false, res);
+      search_local_points(s, true, res);
+      toc();
       break;
     }
     default:

@@ -5,7 +5,9 @@
 // SearchByProjection overloads, SearchForTriangulation, SearchBySim3 and both
 // Fuse overloads (whose map mutations run in the reference's order on the
 // host). Additions, none of which changes a caller: Handle() (the calling
-// thread's device workspace, also used by Frame::ComputeStereoMatches) and a
+// thread's device workspace, also used by Frame::ComputeStereoMatches),
+// SearchLocalPoints (Tracking::SearchLocalPoints' isInFrustum loop and the
+// search after it in one device call) and a
 // private record builder that reads MapPoint::mfMinDistance / mfMaxDistance
 // (a real build adds `friend class ORBmatcher;` to MapPoint).
 #ifndef ORBMATCHER_H
@@ -39,6 +41,15 @@ class ORBmatcher {
                          const float th, const int ORBdist);
   int SearchByProjection(KeyFrame* pKF, cv::Mat Scw, const std::vector<MapPoint*>& vpPoints,
                          std::vector<MapPoint*>& vpMatched, int th);
+
+  // Tracking::SearchLocalPoints' second loop and its SearchByProjection call
+  // (src/Tracking.cc:1250-1278) in one device round trip: Frame::isInFrustum(pMP,
+  // viewingCosLimit) on every point that is not bad and was not seen in F
+  // (mnLastFrameSeen != F.mnId), its mTrack* fields and IncreaseVisible() as
+  // that loop leaves them, then the search over the points in view. Returns the
+  // search's result (0 with nothing in view); *nToMatch = the points in view.
+  int SearchLocalPoints(Frame& F, const std::vector<MapPoint*>& vpLocalMapPoints, const float th,
+                        int* nToMatch = nullptr, const float viewingCosLimit = 0.5f);
 
   int SearchByBoW(KeyFrame* pKF, Frame& F, std::vector<MapPoint*>& vpMapPointMatches);
   int SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, std::vector<MapPoint*>& vpMatches12);

@@ -164,6 +164,45 @@ int ORBmatcher::SearchByProjection(Frame& F, const std::vector<MapPoint*>& vpMap
   return n;
 }
 
+// Tracking::SearchLocalPoints (Tracking.cc:1250-1278): isInFrustum per point and the search above, one call
+int ORBmatcher::SearchLocalPoints(Frame& F, const std::vector<MapPoint*>& vpLocalMapPoints, const float th,
+                                  int* nToMatch, const float viewingCosLimit) {
+  const int M = (int)vpLocalMapPoints.size();
+  std::vector<orbm_map_point_world> mp(std::max(M, 1));
+  for (int j = 0; j < M; ++j) {
+    MapPoint* p = vpLocalMapPoints[j];
+    mp[j] = MapPointRecord(p, 0.f, 0, p && p->mnLastFrameSeen != F.mnId && !p->isBad());
+  }
+  const cv::Mat D = point_descriptors(vpLocalMapPoints);
+  std::vector<uint8_t> blocked(std::max(F.N, 1));
+  for (int i = 0; i < F.N; ++i) blocked[i] = F.mvpMapPoints[i] && F.mvpMapPoints[i]->Observations() > 0;
+  const orbm_camera cur = camera(Frame::fx, Frame::fy, Frame::cx, Frame::cy, F.mb, F.mbf, F.mTcw);
+  std::vector<orbm_map_point_proj> proj(std::max(M, 1));
+  std::vector<int> out(std::max(F.N, 1), -1);
+  int n = 0, inView = 0;
+  orbm_check(orbm_search_local_points(Handle(), kps(F.mvKeysUn), F.mDescriptors.ptr<uint8_t>(), F.N,
+                                      uright(F.mvuRight, F.N), frame_bounds(), F.mvScaleFactors.data(),
+                                      (int)F.mvScaleFactors.size(), F.mfScaleFactor, blocked.data(), &cur, mp.data(),
+                                      D.data, M, viewingCosLimit, th, mfNNratio, out.data(), &n, proj.data(),
+                                      &inView));
+  for (int j = 0; j < M; ++j) {
+    MapPoint* p = vpLocalMapPoints[j];
+    if (!mp[j].valid) continue;  // the reference's loop skips these before isInFrustum
+    p->mbTrackInView = proj[j].track_in_view != 0;
+    if (!p->mbTrackInView) continue;
+    p->mTrackProjX = proj[j].proj_x;
+    p->mTrackProjXR = proj[j].proj_xr;
+    p->mTrackProjY = proj[j].proj_y;
+    p->mnTrackScaleLevel = proj[j].predicted_level;
+    p->mTrackViewCos = proj[j].view_cos;
+    p->IncreaseVisible();
+  }
+  for (int i = 0; i < F.N; ++i)
+    if (out[i] >= 0) F.mvpMapPoints[i] = vpLocalMapPoints[out[i]];
+  if (nToMatch) *nToMatch = inView;
+  return n;
+}
+
 // SearchByProjection(CurrentFrame, LastFrame, th, bMono) (:1328-1470): Tracking::TrackWithMotionModel (Tracking.cc:962, 968)
 int ORBmatcher::SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, const float th, const bool bMono) {
   const int NL = LastFrame.N, NC = CurrentFrame.N;
