@@ -137,8 +137,11 @@ __global__ __launch_bounds__(256) void blur_kernel(ExtractParams P, LevelPtrs lp
   const uint32_t kA1 = (k[0] << 16) | (k[1] << 24), kB1 = k[2] | (k[3] << 8) | (k[4] << 16) | (k[5] << 24), kC1 = k[6];
   const uint32_t kA2 = k[0] << 24, kB2 = k[1] | (k[2] << 8) | (k[3] << 16) | (k[4] << 24), kC2 = k[5] | (k[6] << 8);
   const uint32_t kB3 = k[0] | (k[1] << 8) | (k[2] << 16) | (k[3] << 24), kC3 = k[4] | (k[5] << 8) | (k[6] << 16);
+  // a tile that hangs over the level's last row works on the row pairs that
+  // reach a stored row only (uniform per workgroup: whole waves drop out)
+  const int opairs = (min(kBlurTH, H - y0) + 1) >> 1;  // output row pairs; the row pass feeds 3 more
   // row pass: item = (row pair, 4 columns)
-  for (int i = tid; i < kBlurPairs * (kBlurTW / 4); i += 256) {
+  for (int i = tid; i < min(kBlurPairs, opairs + 3) * (kBlurTW / 4); i += 256) {
     const int pr = i / (kBlurTW / 4), x = (i - pr * (kBlurTW / 4)) * 4;
     uint32_t o[2][4];
 #pragma unroll
@@ -158,7 +161,7 @@ __global__ __launch_bounds__(256) void blur_kernel(ExtractParams P, LevelPtrs lp
   const uint32_t t01 = k[0] | (k[1] << 16), t23 = k[2] | (k[3] << 16), t45 = k[4] | (k[5] << 16), t6 = k[6];
   const uint32_t u0 = k[0] << 16, u12 = k[1] | (k[2] << 16), u34 = k[3] | (k[4] << 16), u56 = k[5] | (k[6] << 16);
   uint8_t* D = blur + g.off + f * g.plane;
-  for (int i = tid; i < (kBlurTH / 2) * (kBlurTW / 4); i += 256) {
+  for (int i = tid; i < opairs * (kBlurTW / 4); i += 256) {
     const int rp = i / (kBlurTW / 4), cx = (i - rp * (kBlurTW / 4)) * 4;
     const uint4 q0 = *(const uint4*)&tmp[rp][cx], q1 = *(const uint4*)&tmp[rp + 1][cx];
     const uint4 q2 = *(const uint4*)&tmp[rp + 2][cx], q3 = *(const uint4*)&tmp[rp + 3][cx];

@@ -320,6 +320,14 @@ static bool plan_pyr_cols(const ExtractParams& P, const std::vector<int2>& rtab,
     }
     C.lpitch[l] = p;
   }
+  // pyr_band_kernel maps its 512 threads to G = ceil(width / 8) column groups
+  // x 512 / G row chunks, and reads aligned dwords from its LDS rows (true
+  // today: level sides are at most 4096 and pitches are rounded to 16)
+  for (int l = 1; l < L; ++l) {
+    if (C.lpitch[l - 1] % 4) return false;
+    for (int c = 0; c < nct; ++c)
+      if (C.chi[c * L + l] - C.lo[c * L + l] + 1 > 8 * 512) return false;
+  }
   return true;
 }
 

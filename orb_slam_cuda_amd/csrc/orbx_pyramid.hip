@@ -144,95 +144,132 @@ __global__ __launch_bounds__(256) void pyr_resize_kernel(
 #define ORBX_PYR_THREADS 512
 #endif
 constexpr int kPyrBandThreads = ORBX_PYR_THREADS;
+// the 2x2 area mean as coefficients of the bilinear loop (band_row): a0 = a1 =
+// 2048, 4*b0 = 4*b1 = 2048
+constexpr uint32_t kPyrAreaA = 2048u | (2048u << 16);
+constexpr int kPyrAreaB4 = 2048 | (2048 << 16);
 // waves per SIMD the band kernel is compiled for (5: <= 96 VGPRs, two
 // 512-thread workgroups per CU; 6 would allow three at <= 53 KB of LDS)
 #ifndef ORBX_PYR_WPE
 #define ORBX_PYR_WPE 5
 #endif
 
-// Rows of one level for one thread: all 32 source bytes of a row pair are
-// read before any is used, so one LDS wait covers them.
-// A thread's 8 output columns are kPyrRuns runs of 8 / kPyrRuns: run k starts
-// at column (8 / kPyrRuns) * (gi + k * G), G = ceil(w / 8). With runs of 2
-// (default) the 32 lanes of an LDS half-wave read source bytes within ~77
-// bytes (20 dwords, distinct banks of ds_read_u8); runs of 4 spread them over
-// ~154 bytes (39 dwords on 32 banks: 2-way conflicts).
-#ifndef ORBX_PYR_RUN
-#define ORBX_PYR_RUN 2
-#endif
-#ifndef ORBX_PYR_ROWFAST
-#define ORBX_PYR_ROWFAST 0  // A/B: thread -> (column group, row) with rows fastest
-#endif
-constexpr int kPyrRun = ORBX_PYR_RUN, kPyrRuns = 8 / kPyrRun;
-static_assert(kPyrRun == 2 || kPyrRun == 4, "runs of 2 or 4 columns");
-__device__ __forceinline__ int pyr_col(int gi, int G, int q) { return kPyrRun * (gi + (q / kPyrRun) * G) + q % kPyrRun; }
+// A thread's 8 output columns are 4 runs of 2: run k starts at column
+// 2 * (gi + k * G), G = ceil(w / 8). The 32 lanes of an LDS half-wave then read
+// source bytes within ~77 bytes (20 dwords, distinct banks).
+__device__ __forceinline__ int pyr_col(int gi, int G, int q) { return 2 * (gi + (q >> 1) * G) + (q & 1); }
 
-// One level of a (band, column tile): rows cd of the level, columns x0 ..
-// x0 + 8G - 1 (G = ceil(comp width / 8) thread groups; sx[] are LDS-relative
-// source columns). Rows and columns owned by the tile go to HBM as well.
-template <bool AREA2X>
-__device__ __forceinline__ void band_rows(const LevelPtrs& lp, int l, int f, const uint8_t* src, int spitch,
-                                          uint8_t* dst, int dpitch, const int2* yt_rows, int src_lo, int2 cd,
-                                          int2 own, int2 ownx, int x0, int r0, int rstep, int gi, int G,
-                                          const int (&sx)[8], const int (&a0v)[8], const int (&a1v)[8]) {
-  uint8_t* G0 = (uint8_t*)lp.base[l] + f * lp.fstride[l];
-  for (int r = cd.x + r0; r <= cd.y; r += rstep) {
-    const int2 yt = yt_rows[r - cd.x];
-    const uint8_t* s0 = src + __mul24((yt.x & 0xFFFF) - src_lo, spitch);
-    const uint8_t* s1 = src + __mul24((yt.x >> 16) - src_lo, spitch);
-    int p00[8], p01[8], p10[8], p11[8];
+typedef unsigned short pyr_us2_t __attribute__((ext_vector_type(2)));
+
+// i / d for 0 <= i < 2^21, d >= 1, given rcp = v_rcp_f32(d), without the ~35
+// instructions of an integer division: (i + 0.5) / d lies at least 0.5 / d from
+// an integer, and the reciprocal's and the product's rounding (relative 2^-22
+// together) move it by at most i / d * 2^-22 < 0.5 / d.
+__device__ __forceinline__ int band_div(int i, float rcp) { return (int)(((float)i + 0.5f) * rcp); }
+
+// Horizontal pass of one source row for a thread's 8 columns. A run's two
+// columns read source bytes sx0, sx0 + 1 and sx1, sx1 + 1 with sx0 <= sx1 <=
+// sx0 + 3 (a scale of at most 2 steps 2 or 3 source columns; a column clamped
+// to the level's last repeats it), all inside the two aligned dwords from
+// sx0 & ~3: one ds_read2_b32 per run (band_load) instead of a byte read per
+// pixel, one v_perm_b32 per column that spreads its pixel pair to u16 x 2
+// (byte selectors fixed per level, BandCols), and one v_dot2_u32_u16 with the
+// column's {a0, a1} (non-negative 11-bit values: the unsigned dot is exact,
+// D <= 255 * 2048 < 2^20). The pair read reaches bytes sx0 & ~3 .. + 7, up to
+// 6 bytes past the last byte a column uses: into the row's padding, the next
+// row, or (from the last row of one buffer) the first bytes of the other
+// buffer or of the staged y entries, which other lanes may be writing. The
+// selectors never pick those bytes, and the kernel's LDS block ends 16 bytes
+// after the y entries, so every read stays inside it. The dword alignment
+// rests on the plan: every LDS row pitch and pyr_lds_a are multiples of 4
+// (plan_pyr_cols rounds pitches to 16; ORBX_PYR_PADMOD steps by 4 or 16). A
+// 16-bit read at the pair's own byte is no
+// substitute: at odd addresses it runs the LDS at a third of the speed
+// (109 us per 32 KITTI frames against 37).
+struct BandCols {
+  int off[4];       // run k: LDS-relative byte offset of its dword pair in a source row (a multiple of 4)
+  uint32_t sel[8];  // column q: v_perm_b32 selector {o, zero, o + 1, zero}, o = the column's byte in the pair
+  uint32_t a01[8];  // column q: a0 | a1 << 16
+};
+__device__ __forceinline__ void band_load(const uint8_t* row, const BandCols& bc, uint32_t (&p)[8]) {
 #pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      p00[q] = s0[sx[q]];
-      p01[q] = s0[sx[q] + 1];
-      p10[q] = s1[sx[q]];
-      p11[q] = s1[sx[q] + 1];
-    }
-    int v[8];
-    if (AREA2X) {
+  for (int k = 0; k < 4; ++k) {
+    const uint32_t* d = (const uint32_t*)(row + bc.off[k]);
+    p[2 * k] = d[0];
+    p[2 * k + 1] = d[1];
+  }
+}
+__device__ __forceinline__ void band_hpass(const uint32_t (&p)[8], const BandCols& bc, uint32_t (&D)[8]) {
 #pragma unroll
-      for (int q = 0; q < 8; ++q) v[q] = (p00[q] + p01[q] + p10[q] + p11[q] + 2) >> 2;
-    } else {
-      const int b0 = (short)(yt.y & 0xFFFF), b1 = (short)(yt.y >> 16);
-      // every factor fits 24 bits (u8 x 11-bit coefficients, D < 2^20): full-rate
-      // v_mad_i32_i24 instead of the quarter-rate 32-bit multiply
+  for (int q = 0; q < 8; ++q) {
+    const uint32_t pp = __builtin_amdgcn_perm(p[q | 1], p[q & ~1], bc.sel[q]);
+    D[q] = __builtin_amdgcn_udot2(__builtin_bit_cast(pyr_us2_t, pp), __builtin_bit_cast(pyr_us2_t, bc.a01[q]), 0u, false);
+  }
+}
+
+// a * b + c for a, b < 2^24 as one v_mad_u32_u24 (from __umul24 and adds the
+// compiler makes two multiplies and a three-operand add per pixel)
+__device__ __forceinline__ uint32_t band_mad24(uint32_t a, uint32_t b, uint32_t c) {
+  uint32_t d;
+  asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
+  return d;
+}
+
+// One output row from the horizontal results Da (source row y0; kept from the
+// previous output row where that row's second source row was y0) and Db
+// (source row y1, always new; it is the next row's candidate for Da).
+// Vertical pass: b0 and b1 arrive x4 (yt.y), so the rounded value
+// (D0*b0 + D1*b1 + 2^21) >> 22 is the top byte of D0*4b0 + D1*4b1 + 2^23:
+// a0 + a1 and b0 + b1 are at most 2049, so the sum is at most
+// 4 * (255 * 2049 * 2049 + 2^21) = 4 290 757 628 < 2^32 with every term >= 0,
+// and its top byte is at most 255: no clamp. The 2x2 area mean runs through the
+// same code with a0 = a1 = 2048 and 4b0 = 4b1 = 2048 (the kernel's constants):
+// ((p00 + p01 + p10 + p11) * 2^22 + 2^23) >> 24 = (sum + 2) >> 2.
+struct BandRowCtx {
+  const uint8_t* src;   // the source level's LDS tile, row src_lo first
+  uint8_t* dst;         // this level's LDS tile
+  uint8_t* g[4];        // the level's plane in HBM + the tile's column origin + 2kG (uniform)
+  const int2* yt;       // staged row entries, row cd.x first
+  int spitch, dpitch, gpitch, src_lo, row0;
+  unsigned own_lo, own_n;  // owned rows: r - own_lo < own_n
+  // hoisted out of the row loop: run k is owned whole by the tile / only its
+  // first column is (the level's last column), and whether any run is such
+  bool st2[4], st1[4], any1;
+};
+__device__ __forceinline__ void band_row(const BandRowCtx& c, int r, uint32_t loff, uint32_t goff, int& have,
+                                         const BandCols& bc, int G, uint32_t (&Da)[8], uint32_t (&Db)[8]) {
+  const int2 yt = c.yt[r - c.row0];
+  const int y0 = yt.x & 0xFFFF, y1 = yt.x >> 16;
+  const uint8_t* const row1 = c.src + __mul24(y1 - c.src_lo, c.spitch);
+  uint32_t p1[8];
+  if (y0 != have) {
+    // the second source row's reads are in flight while the first is redone
+    uint32_t p0[8];
+    band_load(c.src + __mul24(y0 - c.src_lo, c.spitch), bc, p0);
+    band_load(row1, bc, p1);
+    band_hpass(p0, bc, Da);
+  } else {
+    band_load(row1, bc, p1);
+  }
+  band_hpass(p1, bc, Db);
+  have = y1;
+  const uint32_t b0 = (uint32_t)yt.y & 0xFFFFu, b1 = (uint32_t)yt.y >> 16;
+  const bool owned = (unsigned)r - c.own_lo < c.own_n;
+  uint32_t pk[4];
 #pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const int D0 = __mul24(p00[q], a0v[q]) + __mul24(p01[q], a1v[q]);
-        const int D1 = __mul24(p10[q], a0v[q]) + __mul24(p11[q], a1v[q]);
-        v[q] = sat_u8((__mul24(D0, b0) + __mul24(D1, b1) + (1 << 21)) >> 22);
-      }
-    }
-    uint8_t* lrow = dst + __mul24(r - cd.x, dpitch);
-    const bool owned = r >= own.x && r <= own.y;
-    uint8_t* drow = G0 + (long long)r * lp.pitch[l];
-    if constexpr (kPyrRun == 4) {
-      const int xa = pyr_col(gi, G, 0), xb = pyr_col(gi, G, 4);
-      const uint32_t pa = pack4_u8(v[0], v[1], v[2], v[3]), pb = pack4_u8(v[4], v[5], v[6], v[7]);
-      *(uint32_t*)(lrow + xa) = pa;
-      *(uint32_t*)(lrow + xb) = pb;
-      if (owned) {
-        for (int q = 0; q < 4; ++q) {
-          const int ga = x0 + xa + q, gb = x0 + xb + q;
-          if (ga >= ownx.x && ga <= ownx.y) drow[ga] = (uint8_t)(pa >> (8 * q));
-          if (gb >= ownx.x && gb <= ownx.y) drow[gb] = (uint8_t)(pb >> (8 * q));
-        }
-      }
-    } else {
+  for (int k = 0; k < 4; ++k) {
+    const uint32_t va = band_mad24(Da[2 * k], b0, band_mad24(Db[2 * k], b1, 1u << 23));
+    const uint32_t vb = band_mad24(Da[2 * k + 1], b0, band_mad24(Db[2 * k + 1], b1, 1u << 23));
+    pk[k] = __builtin_amdgcn_perm(vb, va, 0x0c0c0703u);  // {va byte 3, vb byte 3, 0, 0}
+    *(uint16_t*)(c.dst + loff + 2 * k * G) = (uint16_t)pk[k];  // the LDS row holds the run even past the computed columns
+    // owned ranges start at even columns (plan_pyr_cols), so a run is owned
+    // whole or not at all, but at the level's last column (below)
+    if (owned && c.st2[k]) *(uint16_t*)(c.g[k] + goff) = (uint16_t)pk[k];
+  }
+  if (c.any1 && owned) {
 #pragma unroll
-      for (int k = 0; k < kPyrRuns; ++k) {
-        const int xk = pyr_col(gi, G, 2 * k);
-        const uint16_t pk = (uint16_t)(sat_u8(v[2 * k]) | (sat_u8(v[2 * k + 1]) << 8));
-        *(uint16_t*)(lrow + xk) = pk;  // the LDS row holds the run even past the computed columns
-        // owned ranges start at even columns (plan_pyr_cols), so a run is
-        // owned whole or not at all, but at the level's last column
-        const int gx = x0 + xk;
-        if (owned && gx >= ownx.x && gx <= ownx.y) {
-          if (gx < ownx.y) *(uint16_t*)(drow + gx) = pk;
-          else drow[gx] = (uint8_t)pk;
-        }
-      }
-    }
+    for (int k = 0; k < 4; ++k)
+      if (c.st1[k]) c.g[k][goff] = (uint8_t)pk[k];
   }
 }
 
@@ -267,8 +304,14 @@ __global__ __launch_bounds__(kPyrBandThreads) __attribute__((amdgpu_waves_per_eu
     }
     ytot += n;
   }
+  // staged entry: {sy0 | sy1 << 16, 4*b0 | 4*b1 << 16} (band_row; 4 * 2048 fits 16 bits)
+  auto y_entry = [&](int area, int tab, int r) {
+    if (area) return make_int2((2 * r) | ((2 * r + 1) << 16), kPyrAreaB4);
+    const int2 e = rtab[tab + r];
+    return make_int2(e.x, e.y << 2);
+  };
   int2 yval = make_int2(0, 0);
-  if (tid < ytot) yval = yarea ? make_int2((2 * yrow) | ((2 * yrow + 1) << 16), 0) : rtab[ytab + yrow];
+  if (tid < ytot) yval = y_entry(yarea, ytab, yrow);
   for (int i = tid + kPyrBandThreads; i < ytot; i += kPyrBandThreads) {  // very tall bands only
     int rem = i;
     for (int l = 1; l < L; ++l) {
@@ -277,7 +320,7 @@ __global__ __launch_bounds__(kPyrBandThreads) __attribute__((amdgpu_waves_per_eu
       if (rem < n) {
         const LevelGeom& g = P.lv[l];
         const int r = cd.x + rem;
-        s_yt[i] = g.area2x ? make_int2((2 * r) | ((2 * r + 1) << 16), 0) : rtab[g.ytab + r];
+        s_yt[i] = y_entry(g.area2x, g.ytab, r);
         break;
       }
       rem -= n;
@@ -294,7 +337,8 @@ __global__ __launch_bounds__(kPyrBandThreads) __attribute__((amdgpu_waves_per_eu
     const uint8_t* S = lp.base[0] + f * lp.fstride[0] + (long long)c0.x * pitch + org;
     if (lp.aligned16[0]) {
       typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-      const int nch = ((xe - org) >> 4) + 1, total = rows * nch;
+      const int nch = ((xe - org) >> 4) + 1, total = rows * nch;  // at most a CU's LDS / 16
+      const float rnch = __builtin_amdgcn_rcpf((float)nch);
       // unpredicated (indices past the end repeat the last chunk)
       for (int i0 = tid; i0 < total; i0 += 4 * kPyrBandThreads) {
         u32x4 v[4];
@@ -302,7 +346,7 @@ __global__ __launch_bounds__(kPyrBandThreads) __attribute__((amdgpu_waves_per_eu
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const int i = min(i0 + q * kPyrBandThreads, total - 1);
-          const int r = i / nch, ch = i - r * nch;
+          const int r = band_div(i, rnch), ch = i - r * nch;
           lo[q] = r * pitch + ch * 16;
           so[q] = r * lp0 + ch * 16;
         }
@@ -323,17 +367,29 @@ __global__ __launch_bounds__(kPyrBandThreads) __attribute__((amdgpu_waves_per_eu
 
   // column coefficients: level l+1's are fetched while level l is computed
   int2 nxt[8];
-  // a thread's 8 columns are kPyrRuns runs (pyr_col) with G = ceil(width/8)
+  int nxt_gi = 0, nxt_ra = 0, nxt_rb = -1;  // the thread's column group and rows [ra, rb] at that level
+  // a thread's 8 columns are 4 runs of 2 (pyr_col) with G = ceil(width/8)
   // over the tile's computed columns: neighbouring lanes read source bytes a
   // run's width x 1.2 apart
   auto fetch_cols = [&](int l) {
     const LevelGeom& g = P.lv[l];
     const int2 xc = xt[3 * l];
-#if ORBX_PYR_ROWFAST
-    const int G = (xc.y - xc.x + 1 + 7) >> 3, gi = min(tid / (kPyrBandThreads / G), G - 1);
-#else
-    const int G = (xc.y - xc.x + 1 + 7) >> 3, gi = tid % G;
-#endif
+    const int G = (xc.y - xc.x + 1 + 7) >> 3;
+    const float rG = __builtin_amdgcn_rcpf((float)G);
+    const int chunk = band_div(tid, rG), gi = tid - chunk * G;
+    // Rows per thread: the level's rows over the kPyrBandThreads / G row chunks
+    // (G <= kPyrBandThreads, so nchunks >= 1: plan_pyr_cols refuses wider
+    // tiles). Chunks differ by at most one row and the longer ones come first,
+    // so the spare rows fill whole waves (a wave takes as long as its longest
+    // lane) and every chunk is used, as when rows were strided. Worked out
+    // here, a level ahead and without integer divisions: two dependent scalar
+    // divisions at the top of a level were ~300 of a short level's ~3 k clocks.
+    const int2 cd = bt[2 * l];
+    const int nrows = cd.y - cd.x + 1, nchunks = band_div(kPyrBandThreads, rG);
+    const int len = band_div(nrows, __builtin_amdgcn_rcpf((float)nchunks)), rem = nrows - len * nchunks;
+    nxt_gi = gi;
+    nxt_ra = cd.x + chunk * len + min(chunk, rem);
+    nxt_rb = chunk < nchunks ? nxt_ra + len - (chunk < rem ? 0 : 1) : nxt_ra - 1;
 #pragma unroll
     for (int q = 0; q < 8; ++q) nxt[q] = rtab[g.xtab2 + min(xc.x + pyr_col(gi, G, q), g.w - 1)];
   };
@@ -341,36 +397,53 @@ __global__ __launch_bounds__(kPyrBandThreads) __attribute__((amdgpu_waves_per_eu
   lds_sync();  // LDS only: the owned rows written to HBM are not read back here
   if (dbg && tid == 0) dbg[blockIdx.x * 16] = (int)(__builtin_amdgcn_s_memtime() - t_begin);
 
-  // ---- levels 1 .. L-1: thread -> 8 output columns (runs of 2), rows strided
+  // ---- levels 1 .. L-1: thread -> 8 output columns (runs of 2) x a contiguous
+  // chunk of the level's computed rows. Walking the chunk, the horizontal
+  // result of a row's second source row stays in registers and serves as the
+  // next row's first whenever the staged y entries say it is the same source
+  // row (four rows out of five at scale 1.2; never on the 2x2 area path, on the
+  // first row of a chunk or after a step of two source rows).
   int yoff = 0;
   for (int l = 1; l < L; ++l) {
     const LevelGeom& g = P.lv[l];
-    const uint8_t* src = (l & 1) ? bufA : bufB;
-    uint8_t* dst = (l & 1) ? bufB : bufA;
     const int2 cs = bt[2 * (l - 1)], cd = bt[2 * l], own = bt[2 * l + 1];
     const int2 xc = xt[3 * l], xo = xt[3 * l + 1], sp = xt[3 * (l - 1) + 2], dp = xt[3 * l + 2];
-    const int G = (xc.y - xc.x + 1 + 7) >> 3, rstep = kPyrBandThreads / G;
-#if ORBX_PYR_ROWFAST
-    // rows fastest: a half-wave's lanes read one column group of ~rstep rows
-    const int gi = tid / rstep, r0 = tid < rstep * G ? tid - gi * rstep : rstep;
-#else
-    const int gi = tid % G, r0 = tid / G;
-#endif
-    int sx[8], a0v[8], a1v[8];
+    const int G = (xc.y - xc.x + 1 + 7) >> 3, gi = nxt_gi, ra = nxt_ra, rb = nxt_rb;
+    BandCols bc;
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
-      sx[q] = nxt[q].x - sp.y;  // LDS-relative: the source level's row starts at column sp.y
-      a0v[q] = (short)(nxt[q].y & 0xFFFF);
-      a1v[q] = (short)(nxt[q].y >> 16);
+      const int sx = nxt[q].x - sp.y;  // LDS-relative: the source level's row starts at column sp.y
+      if (!(q & 1)) bc.off[q >> 1] = sx & ~3;
+      const uint32_t o = (uint32_t)(sx - bc.off[q >> 1]);  // 0 .. 6
+      bc.sel[q] = 0x0c000c00u | o | ((o + 1) << 16);
+      bc.a01[q] = g.area2x ? kPyrAreaA : (uint32_t)nxt[q].y;
     }
     if (l + 1 < L) fetch_cols(l + 1);
-    if (r0 < rstep) {
-      if (g.area2x)
-        band_rows<true>(lp, l, f, src, sp.x, dst, dp.x, s_yt + yoff, cs.x, cd, own, xo, xc.x, r0, rstep, gi, G, sx,
-                        a0v, a1v);
-      else
-        band_rows<false>(lp, l, f, src, sp.x, dst, dp.x, s_yt + yoff, cs.x, cd, own, xo, xc.x, r0, rstep, gi, G, sx,
-                         a0v, a1v);
+    BandRowCtx c;
+    c.src = (l & 1) ? bufA : bufB;
+    c.dst = (l & 1) ? bufB : bufA;
+    c.yt = s_yt + yoff;
+    c.spitch = sp.x, c.dpitch = dp.x, c.gpitch = lp.pitch[l], c.src_lo = cs.x, c.row0 = cd.x;
+    c.own_lo = (unsigned)own.x, c.own_n = (unsigned)(own.y - own.x + 1);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int gx = xc.x + 2 * (gi + k * G);
+      c.g[k] = (uint8_t*)lp.base[l] + f * lp.fstride[l] + xc.x + 2 * k * G;
+      c.st2[k] = gx >= xo.x && gx < xo.y;
+      c.st1[k] = gx == xo.y;
+    }
+    c.any1 = c.st1[0] | c.st1[1] | c.st1[2] | c.st1[3];
+    // 32-bit offsets of the thread's first run in the LDS tile and in the
+    // level's plane (level sides are at most 4096), advanced by a pitch per row
+    uint32_t loff = (uint32_t)(__mul24(ra - cd.x, c.dpitch) + 2 * gi);
+    uint32_t goff = (uint32_t)(ra * c.gpitch + 2 * gi);
+    uint32_t Da[8], Db[8];
+    int have = -1;  // the source row whose horizontal result the next row's Da holds
+    for (int r = ra; r <= rb; r += 2) {
+      band_row(c, r, loff, goff, have, bc, G, Da, Db);
+      loff += c.dpitch, goff += c.gpitch;
+      if (r + 1 <= rb) band_row(c, r + 1, loff, goff, have, bc, G, Db, Da);
+      loff += c.dpitch, goff += c.gpitch;
     }
     yoff += cd.y - cd.x + 1;
     lds_sync();
