@@ -52,7 +52,7 @@ size_t quadtree_sorted_lds_bytes(const ExtractParams& P, int big);
 int quadtree_sorted_ownmax(const ExtractParams& P, int big, size_t budget);
 extern const void* quadtree_kernel_ptr(const ExtractParams& P);
 size_t pyr_band_lds_bytes(const ExtractParams& P);
-void blur_tile_dims(int small, int* tw, int* th);
+void blur_strip_dims(int small, int* strip, int* rows);
 extern const void* pyr_band_kernel_ptr();
 extern int pyr_band_occupancy(size_t lds);
 }  // namespace orbx
@@ -684,15 +684,18 @@ static int build_plan(orbx_extractor* h, int W, int Hh, int B) {
     return fail(ORBX_EINVAL, "max_batch %d: the pyramid planes take %lld bytes, over 2 GiB", B, lvl_off);
   plan_band_pyramid(P, pl.rtab);
   for (int v = 0; v < 2; ++v) {
-    // blur tiles, large and small, level-major, row-major inside a level (orbx_blur.hip)
-    int tw = 0, th = 0;
-    blur_tile_dims(v, &tw, &th);
+    // blur work lists, long and short segments (orbx_blur.hip): one entry per
+    // wave, level-major, a strip's segments top to bottom, so the four waves
+    // of a workgroup mostly share their halo rows
+    int sw = 0, R = 0;
+    blur_strip_dims(v, &sw, &R);
     P.blur_tiles[v] = (int)pl.rtab.size();
     for (int l = 0; l < L; ++l)
-      for (int y0 = 0; y0 < P.lv[l].h; y0 += th)
-        for (int x0 = 0; x0 < P.lv[l].w; x0 += tw) pl.rtab.push_back(make_int2(l | (x0 << 4) | (y0 << 16), 0));
+      for (int x0 = 0; x0 < P.lv[l].w; x0 += sw)
+        for (int y0 = 0; y0 < P.lv[l].h; y0 += R)
+          pl.rtab.push_back(make_int2(l | (x0 << 4) | (y0 << 16), std::min(R, P.lv[l].h - y0)));
     P.blur_ntiles[v] = (int)pl.rtab.size() - P.blur_tiles[v];
-    const unsigned long long d = (unsigned long long)P.blur_ntiles[v];
+    const unsigned long long d = (unsigned long long)(P.blur_ntiles[v] + 3) / 4;  // workgroups per frame
     P.blur_magic[v] = 0u;
     if (d > 1) {
       const unsigned long long m = ((1ull << 32) + d - 1) / d, e = m * d - (1ull << 32);
