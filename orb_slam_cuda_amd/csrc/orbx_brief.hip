@@ -87,6 +87,9 @@ __global__ __launch_bounds__(kObThreads) void orient_brief_kernel(ExtractParams 
   __shared__ __attribute__((aligned(16))) uint8_t s_patch[kObKps][kObRows * kObStride];
   __shared__ float4 s_tests[256];
   __shared__ uint32_t s_ictab[16 * kIcStride];
+  // glibc_sincosf's coefficient tables: read from global memory they put two
+  // more dependent round trips behind the angle
+  __shared__ SinCosfTable s_sincos[2];
   const int wg = xcd_remap(blockIdx.x + blockIdx.y * gridDim.x, gridDim.x * gridDim.y);
   const int bx = wg % gridDim.x, f = wg / gridDim.x, tid = threadIdx.x;
   const int lane = tid & 31, hk = tid >> 5;  // keypoint of this half-wave within the workgroup
@@ -108,6 +111,9 @@ __global__ __launch_bounds__(kObThreads) void orient_brief_kernel(ExtractParams 
   for (int k = 0; k < kTestsPer; ++k) test_v[k] = c_brief_tests[P.pattern_upstream ? 1 : 0][min(tid + k * kObThreads, 255)];
 #pragma unroll
   for (int k = 0; k < kIcPer; ++k) ic_v[k] = c_ic_coef[min(tid + k * kObThreads, 16 * 24 - 1)];
+  constexpr int kSincosDoubles = 2 * (int)(sizeof(SinCosfTable) / sizeof(double));
+  static_assert(kSincosDoubles <= kObThreads, "one entry per thread");
+  const double sincos_v = ((const double*)&sincosf_table(0))[min(tid, kSincosDoubles - 1)];
 
   // the workgroup's level, in scalar code: level slot ranges start at
   // multiples of kKpGroup (= kObKps) slots, so all of a workgroup's keypoints
@@ -189,6 +195,7 @@ __global__ __launch_bounds__(kObThreads) void orient_brief_kernel(ExtractParams 
       const int i = tid + k * kObThreads;
       s_ictab[(i / 24) * kIcStride + i % 24] = ic_v[k];
     }
+  if (tid < kSincosDoubles) ((double*)s_sincos)[tid] = sincos_v;
   // an empty slot writes its own unused patch; the loads hold row
   // (lane / 4) + 8k, and the rows past the patch are not stored
   {
@@ -205,7 +212,7 @@ __global__ __launch_bounds__(kObThreads) void orient_brief_kernel(ExtractParams 
       }
     }
   }
-  __syncthreads();  // staged patch, test table, IC coefficient table
+  __syncthreads();  // staged patch, test table, IC coefficient table, sincosf tables
 
   // ---- IC_Angle (:164-191): per row, the pixels weighted with v_dot4_u32_u8
   // against coefficient dwords (u for u > 0 / -u for u < 0 / 1, inside the
@@ -232,7 +239,7 @@ __global__ __launch_bounds__(kObThreads) void orient_brief_kernel(ExtractParams 
   // computeOrbDescriptor: a = cosf(angle*pi/180), b = sinf(...), glibc's (orbx_sincosf.h)
   const float factorPI = (float)(M_PI / 180.f);
   float a, b;
-  glibc_sincosf(__fmul_rn(angle, factorPI), &b, &a);
+  glibc_sincosf(__fmul_rn(angle, factorPI), &b, &a, s_sincos);
 
   // GET_VALUE(idx): center[cvRound(x*b + y*a)*step + cvRound(x*a - y*b)]
   const uint8_t* pc = s_patch[hk] + kObRadius * kObStride + (x - c0);

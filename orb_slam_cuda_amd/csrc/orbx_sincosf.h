@@ -55,7 +55,9 @@ __host__ __device__ inline float sincosf_cospoly(const SinCosfTable& p, double x
   return (float)sincosf_fma(b, x6, c);
 }
 
-__host__ __device__ inline void glibc_sincosf(float y, float* sn, float* cs) {
+// T: the two tables of sincosf_table, wherever the caller keeps them (a kernel
+// that must not wait for a global load here stages them in LDS)
+__host__ __device__ inline void glibc_sincosf(float y, float* sn, float* cs, const SinCosfTable* T) {
   uint32_t u;
   __builtin_memcpy(&u, &y, 4);
   const uint32_t top12 = (u >> 20) & 0x7ff;
@@ -67,16 +69,16 @@ __host__ __device__ inline void glibc_sincosf(float y, float* sn, float* cs) {
       return;
     }
     const double x2 = x * x;
-    *sn = sincosf_sinpoly(sincosf_table(0), x, x2);
-    *cs = sincosf_cospoly(sincosf_table(0), x2);
+    *sn = sincosf_sinpoly(T[0], x, x2);
+    *cs = sincosf_cospoly(T[0], x2);
     return;
   }
-  const SinCosfTable& t0 = sincosf_table(0);
+  const SinCosfTable& t0 = T[0];
   const double r = x * t0.hpi_inv;
   const int n = ((int)r + 0x800000) >> 24;                // round(x * 2/pi)
   const double xr = sincosf_fma(-(double)n, t0.hpi, x);   // x - n*pi/2, one rounding
   const double x2 = xr * xr;
-  const SinCosfTable& p = sincosf_table((n & 2) ? 1 : 0);
+  const SinCosfTable& p = T[(n & 2) ? 1 : 0];
   const double xs = xr * t0.sign[n & 3];
   if (n & 1) {
     *sn = sincosf_cospoly(p, x2);
@@ -85,6 +87,10 @@ __host__ __device__ inline void glibc_sincosf(float y, float* sn, float* cs) {
     *sn = sincosf_sinpoly(p, xs, x2);
     *cs = sincosf_cospoly(p, x2);
   }
+}
+
+__host__ __device__ inline void glibc_sincosf(float y, float* sn, float* cs) {
+  glibc_sincosf(y, sn, cs, &sincosf_table(0));
 }
 
 }  // namespace orbx
