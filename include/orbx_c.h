@@ -39,6 +39,16 @@
  *                          include/Frame.h:82, src/Frame.cc:465-639
  *   orbm_stereo_frame      the stereo Frame constructor's two ExtractORB
  *                          threads + ComputeStereoMatches, src/Frame.cc:77-89
+ *   orbx_undistort_points  cv::undistortPoints(src, dst, K, dist, Mat(), K) as
+ *                          Frame calls it (OpenCV 3.x, five fixed iterations)
+ *   orbx_undistort_keypoints / orbx_frame_tail_batch  Frame::UndistortKeyPoints
+ *                          src/Frame.cc:403-433 (+ ComputeStereoFromRGBD :642-663
+ *                          with the convertTo of src/Tracking.cc:276-277)
+ *   orbx_image_bounds      Frame::ComputeImageBounds  src/Frame.cc:435-463
+ *   orbx_rgbd_frame        the RGB-D Frame constructor's ExtractORB +
+ *                          UndistortKeyPoints + ComputeStereoFromRGBD,
+ *                          src/Frame.cc:134-144 (no depth: the monocular
+ *                          constructor's :189-197)
  *   orbm_search_by_projection  ORBmatcher::SearchByProjection(Frame&,
  *                          const vector<MapPoint*>&, th)  include/ORBmatcher.h:48,
  *                          src/ORBmatcher.cc:45-126 (Tracking::SearchLocalPoints)
@@ -717,6 +727,68 @@ int orbm_compute_stereo_matches_batch(
     const int* d_nL, const orbx_kp* d_kpR, const uint8_t* d_descR,
     const int* d_nR, int kp_pitch, int pairs, float mb, float mbf,
     float* d_uRight, float* d_depth, int* d_nkept, void* stream);
+
+/* ------------- the Frame constructors' tail: UndistortKeyPoints, RGB-D depth
+ * Camera.fx .. Camera.k3 of the settings file as Tracking stores them in mK
+ * and mDistCoef (floats; k3 = 0 when the file has none). 36 bytes. */
+typedef struct orbx_calib {
+  float fx, fy, cx, cy, k1, k2, p1, p2, k3;
+} orbx_calib;
+
+/* Element type of a raw depth image (imDepth before GrabImageRGBD's convertTo). */
+#define ORBX_DEPTH_U16 0 /* CV_16U, TUM's png */
+#define ORBX_DEPTH_F32 1 /* CV_32F            */
+
+/* cv::undistortPoints(src, dst, K, dist, Mat(), K) for n points (xy: x, y
+ * pairs), the OpenCV 3.x scalar loop in double: five fixed-point iterations,
+ * no early exit, no icdist guard. The raw call: no k1 == 0 shortcut. Host
+ * only; the kernels evaluate the same function. xy_out may be xy. */
+int orbx_undistort_points(const orbx_calib* calib, const float* xy, int n, float* xy_out);
+
+/* Frame::ComputeImageBounds (src/Frame.cc:435-463) for a w x h image: the
+ * undistorted corners' extremes when k1 != 0, the image rectangle when
+ * k1 == 0 (whatever the other coefficients are). Host only. */
+int orbx_image_bounds(const orbx_calib* calib, int w, int h, orbm_grid_bounds* out);
+
+/* Frame::UndistortKeyPoints (src/Frame.cc:403-433) on host buffers, computed
+ * on the device (synchronous): kps_un[i] = kps[i] with pt undistorted; a
+ * bitwise copy when k1 == 0 (:405-409). n = 0 is ORBX_OK. */
+int orbx_undistort_keypoints(const orbx_calib* calib, const orbx_kp* kps, int n, orbx_kp* kps_un);
+
+/* The same device-resident and batched, asynchronous on `stream`, in the
+ * layout orbx_extract_batch writes: frame f's d_counts[f] keypoints at
+ * d_kps + f*kp_pitch, outputs at the same pitch; slots from d_counts[f] on
+ * are not written. With a depth image (frame f at d_depth_img +
+ * f*depth_frame_pitch, rows of w elements of depth_type at depth_row_stride
+ * bytes, both multiples of the element size) it is also
+ * Frame::ComputeStereoFromRGBD (src/Frame.cc:642-663): d = the pixel under
+ * the distorted keypoint ((int)y, (int)x), converted as GrabImageRGBD's
+ * convertTo(CV_32F, depth_factor) does ((float)raw * depth_factor iff
+ * |depth_factor - 1| > 1e-5 or the type is not F32; depth_factor is
+ * mDepthMapFactor, the inverse of the settings file's value,
+ * src/Tracking.cc:150-154); d > 0: d_depth = d, d_uRight = x_undistorted -
+ * mbf / d; otherwise both -1. A keypoint outside the image (undefined in the
+ * reference) gets -1. d_depth_img == NULL: undistortion only, d_uRight and
+ * d_depth are not touched and may be NULL. */
+int orbx_frame_tail_batch(const orbx_calib* calib, const orbx_kp* d_kps, const int* d_counts, int kp_pitch,
+                          int batch, const void* d_depth_img, int depth_type, size_t depth_frame_pitch,
+                          size_t depth_row_stride, int w, int h, float depth_factor, float mbf,
+                          orbx_kp* d_kps_un, float* d_uRight, float* d_depth, void* stream);
+
+/* The RGB-D Frame constructor's ExtractORB, UndistortKeyPoints and
+ * ComputeStereoFromRGBD (src/Frame.cc:134-144) with one device round trip:
+ * the raw depth image is staged and uploaded while the gray image's
+ * extraction runs, the tail kernel follows the extraction's last kernel on
+ * the handle's stream and all outputs come back in the same wait. kps / desc / *n equal orbx_extract's
+ * on the same image; kps_un, uRight, depth: cap entries, *n written.
+ * depth_img == NULL: the monocular constructor (:189-197), uRight and depth
+ * (when not NULL) are filled with -1. An empty image (w or h_ 0): *n = 0.
+ * ORBX_EINVAL: a null calib, an unknown depth_type, depth_stride < w *
+ * element size, cap below orbx_frame_capacity(h), or a handle planned for
+ * another size than w x h_ (orbx_extract re-plans, this call does not). */
+int orbx_rgbd_frame(orbx_handle h, const uint8_t* img, size_t stride, const void* depth_img, int depth_type,
+                    size_t depth_stride, int w, int h_, const orbx_calib* calib, float depth_factor, float mbf,
+                    orbx_kp* kps, int cap, uint8_t* desc, int* n, orbx_kp* kps_un, float* uRight, float* depth);
 
 /* ------------------------------------------------------ vocabulary (DBoW2) */
 typedef struct orbv_vocabulary* orbv_handle;

@@ -38,6 +38,26 @@ class GridBounds(C.Structure):
     _fields_ = [("min_x", C.c_float), ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float)]
 
 
+class OrbxCalib(C.Structure):
+    """orbx_calib: Camera.fx, fy, cx, cy and k1, k2, p1, p2, k3 (mK / mDistCoef), 36 bytes."""
+    _fields_ = [(k, C.c_float) for k in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3")]
+
+
+assert C.sizeof(OrbxCalib) == 36
+ORBX_DEPTH_U16, ORBX_DEPTH_F32 = 0, 1
+
+
+def calib(K, distCoef) -> OrbxCalib:
+    """orbx_calib from mK (3x3) and mDistCoef (4 values, or 5 with k3), as floats."""
+    K = np.asarray(K, np.float32)
+    d = np.asarray(distCoef, np.float32).reshape(-1)
+    if K.shape != (3, 3) or len(d) not in (4, 5):
+        raise OrbxError(ORBX_EINVAL, "K must be 3x3 and distCoef hold 4 or 5 values")
+    k3 = float(d[4]) if len(d) == 5 else 0.0
+    return OrbxCalib(float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2]), float(d[0]), float(d[1]),
+                     float(d[2]), float(d[3]), k3)
+
+
 class OrbmCamera(C.Structure):
     """orbm_camera: fx, fy, cx, cy, mb, mbf and mTcw rows 0..2 (row-major)."""
     _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
@@ -260,6 +280,16 @@ def lib() -> C.CDLL:
         L.orbx_event_elapsed_ms.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
         L.orbx_stream_wait_event.argtypes = [C.c_void_p, C.c_void_p]
         L.orbx_sincosf_glibc.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.orbx_undistort_points.argtypes = [C.POINTER(OrbxCalib), C.c_void_p, C.c_int, C.c_void_p]
+        L.orbx_image_bounds.argtypes = [C.POINTER(OrbxCalib), C.c_int, C.c_int, C.POINTER(GridBounds)]
+        L.orbx_undistort_keypoints.argtypes = [C.POINTER(OrbxCalib), C.c_void_p, C.c_int, C.c_void_p]
+        L.orbx_frame_tail_batch.argtypes = [
+            C.POINTER(OrbxCalib), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_size_t,
+            C.c_size_t, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.orbx_rgbd_frame.argtypes = [
+            C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_size_t, C.c_int, C.c_int,
+            C.POINTER(OrbxCalib), C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int),
+            C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 

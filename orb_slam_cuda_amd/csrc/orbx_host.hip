@@ -151,6 +151,16 @@ struct orbx_extractor {
   long long h_pyr_off[kMaxLevels] = {};  // level l's offset in h_pyr (l >= 1)
   hipStream_t pstream = nullptr;         // the copy branch's stream (capture fork)
   hipEvent_t pev[2] = {};                // pyramid done, copy done
+  // orbx_rgbd_frame: the raw depth image (pinned staging and its device copy,
+  // rows at a 64-byte pitch; uploaded on dstream beside the extraction, joined
+  // by dev) and the tail kernel's outputs {cap keypoints, cap uRight, cap
+  // depth}, which the kernel stores straight into pinned host memory
+  DeviceBuf d_depth;
+  void* h_depth = nullptr;
+  void* h_tail = nullptr;
+  size_t h_depth_bytes = 0, h_tail_bytes = 0;
+  hipStream_t dstream = nullptr;
+  hipEvent_t dev = nullptr;  // depth upload done
   // ORBX_EXTRACT_PROF=1 (diagnostics): orbx_extract's host phases per call
   // (s), their medians printed by orbx_destroy: staging copy, issue, wait, copy-out
   std::vector<float> prof_t[4];
@@ -983,6 +993,11 @@ int orbx_destroy(orbx_handle h) {
   if (h->h_in) (void)hipHostFree(h->h_in);
   if (h->h_out) (void)hipHostFree(h->h_out);
   if (h->h_pyr) (void)hipHostFree(h->h_pyr);
+  if (h->dstream) (void)hipStreamSynchronize(h->dstream);
+  if (h->h_depth) (void)hipHostFree(h->h_depth);
+  if (h->h_tail) (void)hipHostFree(h->h_tail);
+  if (h->dev) (void)hipEventDestroy(h->dev);
+  if (h->dstream) (void)hipStreamDestroy(h->dstream);
   for (auto& e : h->pev)
     if (e) (void)hipEventDestroy(e);
   if (h->pstream) (void)hipStreamDestroy(h->pstream);
@@ -1276,6 +1291,164 @@ int orbx_extract(orbx_handle h, const uint8_t* img, int w, int hh, size_t stride
     h->prof_t[1].push_back((float)(t2 - t1));
     h->prof_t[2].push_back((float)(t3 - t2));
     h->prof_t[3].push_back((float)(t4 - t3));
+  }
+  return ORBX_OK;
+}
+
+// ------------------------------------------- the Frame constructors' tail
+static size_t depth_elem_size(int depth_type) {
+  return depth_type == ORBX_DEPTH_U16 ? 2 : depth_type == ORBX_DEPTH_F32 ? 4 : 0;
+}
+
+static FrameTailParams tail_params(const orbx_calib& c, int kp_pitch, int depth_type, size_t frame_pitch,
+                                   size_t row_stride, int w, int hh, float factor, float mbf) {
+  FrameTailParams P{};
+  P.calib = c;
+  P.kp_pitch = kp_pitch;
+  P.depth_type = depth_type;
+  P.convert = fabsf(factor - 1.0f) > 1e-5f || depth_type != ORBX_DEPTH_F32;  // src/Tracking.cc:276
+  P.w = w;
+  P.h = hh;
+  P.factor = factor;
+  P.mbf = mbf;
+  P.depth_frame_pitch = frame_pitch;
+  P.depth_row_stride = row_stride;
+  return P;
+}
+
+int orbx_undistort_points(const orbx_calib* calib, const float* xy, int n, float* xy_out) {
+  if (!calib || n < 0 || (n && (!xy || !xy_out))) return fail(ORBX_EINVAL, "orbx_undistort_points: bad argument");
+  undistort_points_host(*calib, xy, n, xy_out);
+  return ORBX_OK;
+}
+
+int orbx_image_bounds(const orbx_calib* calib, int w, int hh, orbm_grid_bounds* out) {
+  if (!calib || !out || w < 0 || hh < 0) return fail(ORBX_EINVAL, "orbx_image_bounds: bad argument");
+  image_bounds_host(*calib, w, hh, out);
+  return ORBX_OK;
+}
+
+int orbx_frame_tail_batch(const orbx_calib* calib, const orbx_kp* d_kps, const int* d_counts, int kp_pitch,
+                          int batch, const void* d_depth_img, int depth_type, size_t depth_frame_pitch,
+                          size_t depth_row_stride, int w, int hh, float depth_factor, float mbf,
+                          orbx_kp* d_kps_un, float* d_uRight, float* d_depth, void* stream) {
+  if (!calib) return fail(ORBX_EINVAL, "orbx_frame_tail_batch: null calib");
+  if (batch < 0 || kp_pitch < 0) return fail(ORBX_EINVAL, "orbx_frame_tail_batch: negative batch or kp_pitch");
+  if (batch == 0 || kp_pitch == 0) return ORBX_OK;
+  if (!d_kps || !d_counts || !d_kps_un) return fail(ORBX_EINVAL, "orbx_frame_tail_batch: null keypoint buffer");
+  if (d_depth_img) {
+    const size_t es = depth_elem_size(depth_type);
+    if (!es) return fail(ORBX_EINVAL, "orbx_frame_tail_batch: unknown depth_type %d", depth_type);
+    if (w < 0 || hh < 0 || depth_row_stride < (size_t)w * es)
+      return fail(ORBX_EINVAL, "orbx_frame_tail_batch: depth_row_stride %zu below %d elements of %zu bytes",
+                  depth_row_stride, w, es);
+    if (depth_row_stride % es || depth_frame_pitch % es || (uintptr_t)d_depth_img % es)
+      return fail(ORBX_EINVAL, "orbx_frame_tail_batch: depth image not aligned to its %zu-byte elements", es);
+    if (batch > 1 && depth_frame_pitch < depth_row_stride * (size_t)hh)
+      return fail(ORBX_EINVAL, "orbx_frame_tail_batch: depth_frame_pitch %zu below one frame", depth_frame_pitch);
+    if (!d_uRight || !d_depth) return fail(ORBX_EINVAL, "orbx_frame_tail_batch: null uRight / depth output");
+  }
+  const FrameTailParams P = tail_params(*calib, kp_pitch, depth_type, depth_frame_pitch, depth_row_stride, w, hh,
+                                        depth_factor, mbf);
+  if (launch_frame_tail(P, d_kps, d_counts, batch, d_depth_img, d_kps_un, d_uRight, d_depth, stream))
+    return fail(ORBX_EDEVICE, "frame tail launch failed: %s", hipGetErrorString(hipGetLastError()));
+  return ORBX_OK;
+}
+
+int orbx_undistort_keypoints(const orbx_calib* calib, const orbx_kp* kps, int n, orbx_kp* kps_un) {
+  if (!calib || n < 0 || (n && (!kps || !kps_un))) return fail(ORBX_EINVAL, "orbx_undistort_keypoints: bad argument");
+  if (n == 0) return ORBX_OK;
+  const size_t kb = (size_t)n * sizeof(orbx_kp);
+  DeviceBuf in, out;  // in: the count (16 bytes) + the keypoints
+  int rc;
+  if ((rc = in.alloc(16 + kb)) || (rc = out.alloc(kb))) return rc;
+  HIP_OK(hipMemcpy(in.p, &n, sizeof n, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(in.as<uint8_t>() + 16, kps, kb, hipMemcpyHostToDevice));
+  if ((rc = orbx_frame_tail_batch(calib, (const orbx_kp*)(in.as<uint8_t>() + 16), in.as<int>(), n, 1, nullptr, 0, 0, 0,
+                                  0, 0, 1.f, 0.f, out.as<orbx_kp>(), nullptr, nullptr, nullptr)))
+    return rc;
+  HIP_OK(hipMemcpy(kps_un, out.p, kb, hipMemcpyDeviceToHost));  // the null stream: after the kernel
+  return ORBX_OK;
+}
+
+int orbx_rgbd_frame(orbx_handle h, const uint8_t* img, size_t stride, const void* depth_img, int depth_type,
+                    size_t depth_stride, int w, int hh, const orbx_calib* calib, float depth_factor, float mbf,
+                    orbx_kp* kps, int cap, uint8_t* desc, int* n, orbx_kp* kps_un, float* uRight, float* depth) {
+  if (!h || !n) return fail(ORBX_EINVAL, "null argument");
+  if (!calib) return fail(ORBX_EINVAL, "orbx_rgbd_frame: null calib");
+  const size_t es = depth_elem_size(depth_type);
+  if (!es) return fail(ORBX_EINVAL, "orbx_rgbd_frame: unknown depth_type %d", depth_type);
+  std::lock_guard<std::mutex> lk(h->mu);
+  *n = 0;
+  if (w == 0 || hh == 0) {
+    extract_empty(h);
+    return ORBX_OK;
+  }
+  if (w < 0 || hh < 0) return fail(ORBX_EINVAL, "bad image");
+  if (depth_img && depth_stride < (size_t)w * es)
+    return fail(ORBX_EINVAL, "orbx_rgbd_frame: depth_stride %zu below %d elements of %zu bytes", depth_stride, w, es);
+  if (w != h->plan.W || hh != h->plan.H)
+    return fail(ORBX_EINVAL, "orbx_rgbd_frame: the handle is planned for %d x %d, not %d x %d", h->plan.W, h->plan.H,
+                w, hh);
+  const int cap_frame = h->plan.P.kp_per_frame;
+  if (cap < cap_frame) return fail(ORBX_EINVAL, "orbx_rgbd_frame: cap %d below the handle's capacity %d", cap, cap_frame);
+  if (!kps_un || (depth_img && (!uRight || !depth))) return fail(ORBX_EINVAL, "orbx_rgbd_frame: null output");
+  int rc = extract_prepare(h, img, w, hh, stride);
+  if (rc) return rc;
+  // the tail's outputs: cap keypoints, cap uRight, cap depth, in pinned host memory
+  const size_t ur_off = (size_t)cap_frame * sizeof(orbx_kp), dp_off = ur_off + (size_t)cap_frame * 4;
+  const size_t tail_bytes = depth_img ? dp_off + (size_t)cap_frame * 4 : ur_off;
+  const size_t dpitch = ((size_t)w * es + 63) & ~(size_t)63;
+  if ((rc = host_reserve(&h->h_tail, &h->h_tail_bytes, tail_bytes))) return rc;
+  void* tail_dev = nullptr;
+  HIP_OK(hipHostGetDevicePointer(&tail_dev, h->h_tail, 0));
+  if (depth_img) {
+    if (h->d_depth.n < dpitch * hh && (rc = h->d_depth.alloc(dpitch * hh))) return rc;
+    if ((rc = host_reserve(&h->h_depth, &h->h_depth_bytes, dpitch * hh))) return rc;
+    if (!h->dstream) HIP_OK(hipStreamCreateWithFlags(&h->dstream, hipStreamNonBlocking));
+    if (!h->dev) HIP_OK(hipEventCreateWithFlags(&h->dev, hipEventDisableTiming));
+  }
+  extract_stage(h, img, w, hh, stride);
+  if ((rc = extract_issue(h, w, hh, false))) return rc;
+  // from here on the device is extracting: a failure waits for it before it returns
+  auto issue_tail = [&]() -> int {
+    if (depth_img) {
+      // the depth image is staged while the extraction runs and uploaded on its
+      // own stream; the handle's stream waits for it before the tail kernel
+      for (int y = 0; y < hh; ++y)
+        memcpy((uint8_t*)h->h_depth + (size_t)y * dpitch, (const uint8_t*)depth_img + (size_t)y * depth_stride,
+               (size_t)w * es);
+      HIP_OK(hipMemcpyAsync(h->d_depth.p, h->h_depth, dpitch * hh, hipMemcpyHostToDevice, h->dstream));
+      HIP_OK(hipEventRecord(h->dev, h->dstream));
+      HIP_OK(hipStreamWaitEvent(h->stream, h->dev, 0));
+    }
+    // after the extraction's last kernel, on its stream: a plain launch on the
+    // count and keypoints where the chain left them
+    uint8_t* d = h->d_out.as<uint8_t>();
+    uint8_t* t = (uint8_t*)tail_dev;
+    const FrameTailParams P = tail_params(*calib, cap_frame, depth_type, dpitch * hh, dpitch, w, hh, depth_factor, mbf);
+    if (launch_frame_tail(P, (const orbx_kp*)(d + 16), (const int*)d, 1, depth_img ? h->d_depth.p : nullptr,
+                          (orbx_kp*)t, (float*)(t + ur_off), (float*)(t + dp_off), h->stream))
+      return fail(ORBX_EDEVICE, "frame tail launch failed: %s", hipGetErrorString(hipGetLastError()));
+    return ORBX_OK;
+  };
+  rc = issue_tail();
+  if (rc) {
+    if (h->dstream) (void)hipStreamSynchronize(h->dstream);
+    (void)hipStreamSynchronize(h->stream);
+    return rc;
+  }
+  HIP_OK(hipStreamSynchronize(h->stream));
+  if ((rc = extract_finish(h, kps, cap, desc, n))) return rc;
+  const size_t cnt = (size_t)*n;
+  const uint8_t* o = (const uint8_t*)h->h_tail;
+  memcpy(kps_un, o, cnt * sizeof(orbx_kp));
+  if (depth_img) {
+    memcpy(uRight, o + ur_off, cnt * 4);
+    memcpy(depth, o + dp_off, cnt * 4);
+  } else {  // the monocular constructor: no stereo information (src/Frame.cc:200-201)
+    if (uRight) std::fill(uRight, uRight + cnt, -1.f);
+    if (depth) std::fill(depth, depth + cnt, -1.f);
   }
   return ORBX_OK;
 }

@@ -450,4 +450,24 @@ int extract_pair(orbx_handle L, orbx_handle R, const uint8_t* imL, size_t stride
                  int capL, uint8_t* descL, int* nL, orbx_kp* kpsR, int capR, uint8_t* descR, int* nR,
                  double* stamps = nullptr);  // diagnostics: host clock after each of its 7 phases
 
+// orbx_frametail.hip: the Frame constructors' tail after ExtractORB
+// (UndistortKeyPoints, ComputeStereoFromRGBD). Uniform per launch; passed to
+// the kernel by value.
+struct FrameTailParams {
+  orbx_calib calib;
+  int kp_pitch;        // keypoint slots per frame (input and outputs)
+  int depth_type;      // ORBX_DEPTH_*
+  int convert;         // the sampled pixel is multiplied by `factor` (depth_converts)
+  int w, h;            // depth image size
+  float factor, mbf;
+  size_t depth_frame_pitch, depth_row_stride;  // bytes
+};
+// frame f: counts[f] keypoints at kps + f*kp_pitch -> kps_un (+ uright, depth
+// when depth_img is not null); slots from counts[f] on are not written
+int launch_frame_tail(const FrameTailParams& P, const orbx_kp* kps, const int* counts, int batch,
+                      const void* depth_img, orbx_kp* kps_un, float* uright, float* depth, void* stream);
+// cv::undistortPoints for n host points (x, y pairs); Frame::ComputeImageBounds
+void undistort_points_host(const orbx_calib& c, const float* xy, int n, float* xy_out);
+void image_bounds_host(const orbx_calib& c, int w, int h, orbm_grid_bounds* out);
+
 }  // namespace orbx

@@ -115,6 +115,22 @@ class ORBextractor:
         check(lib().orbx_extract_batch(self._h, C.c_void_p(d_frames), batch, frame_pitch, row_stride,
                                        C.c_void_p(d_kps), C.c_void_p(d_desc), C.c_void_p(d_counts), s))
 
+    def frame_tail_batch_device(self, K, distCoef, d_kps: int, d_counts: int, kp_pitch: int, batch: int,
+                                d_kps_un: int, *, d_depth_img: int = 0, depth_type: int = _lib.ORBX_DEPTH_U16,
+                                depth_frame_pitch: int = 0, depth_row_stride: int = 0, width: int = 0,
+                                height: int = 0, depth_factor: float = 1.0, mbf: float = 0.0, d_uRight: int = 0,
+                                d_depth: int = 0, stream=None) -> None:
+        """Frame::UndistortKeyPoints (and ComputeStereoFromRGBD when d_depth_img is given) on the
+        device outputs of extract_batch_device, asynchronous (orbx_frame_tail_batch). depth_factor
+        is mDepthMapFactor, the multiplier (the inverse of the settings file's DepthMapFactor)."""
+        s = stream.s if stream is not None else C.c_void_p(0)
+        c = _lib.calib(K, distCoef)
+        check(lib().orbx_frame_tail_batch(
+            C.byref(c), C.c_void_p(d_kps), C.c_void_p(d_counts), int(kp_pitch), int(batch),
+            C.c_void_p(d_depth_img), int(depth_type), int(depth_frame_pitch), int(depth_row_stride), int(width),
+            int(height), C.c_float(depth_factor), C.c_float(mbf), C.c_void_p(d_kps_un), C.c_void_p(d_uRight),
+            C.c_void_p(d_depth), s))
+
     # ------------------------------------------------------------- getters
     def GetLevels(self) -> int:
         return self.nlevels

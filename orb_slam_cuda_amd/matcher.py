@@ -18,6 +18,13 @@ Mirrors include/ORBmatcher.h:37-102 for the hot-path searches:
     nfound   = m.SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th)
     ORBmatcher.DescriptorDistance(a, b)
 
+and for the Frame constructors' tail (src/Frame.cc:118-227, 403-463, 642-663):
+
+    F = ExtractRGBD(extractor, imGray, imDepth, K, distCoef, mbf, DepthMapFactor)  # one device round trip
+    mvKeysUn = UndistortKeyPoints(mvKeys, K, distCoef)
+    mnMinX, mnMaxX, mnMinY, mnMaxY = ComputeImageBounds(width, height, K, distCoef)
+    mvuRight, mvDepth = ComputeStereoFromRGBD(mvKeys, mvKeysUn, imDepth, DepthMapFactor, mbf)
+
 `Frame` / `KeyFrame` here are plain containers of the fields these searches
 read (mvKeysUn, mDescriptors, the grid bounds, camera and pose, mFeatVec,
 MapPoint links). MapPoint pointers are row indices into a `MapPoints` table
@@ -118,6 +125,7 @@ class Frame:
     mvbOutlier: np.ndarray | None = None   # (N,) bool
     mfScaleFactor: float = 1.2
     mpMap: "MapPoints | None" = None
+    mvKeysDistorted: np.ndarray | None = None  # mvKeys where UndistortKeyPoints moved them (k1 != 0)
 
     @property
     def N(self) -> int:
@@ -125,7 +133,7 @@ class Frame:
 
     @property
     def mvKeys(self) -> np.ndarray:
-        return self.mvKeysUn
+        return self.mvKeysUn if self.mvKeysDistorted is None else self.mvKeysDistorted
 
     def isInFrustum(self, mps_idx, viewingCosLimit: float = 0.5) -> np.ndarray:
         """Frame::isInFrustum (src/Frame.cc:268-324) for the MapPoints mps_idx (rows of self.mpMap, -1 =
@@ -143,9 +151,133 @@ class Frame:
         return out
 
     @classmethod
-    def from_extraction(cls, kps, desc, width, height, featvec=None):
-        # no distortion: mvKeysUn == mvKeys and bounds = image rectangle (src/Frame.cc:458-461)
-        return cls(kps, desc, 0.0, float(width), 0.0, float(height), featvec)
+    def from_extraction(cls, kps, desc, width, height, featvec=None, K=None, distCoef=None):
+        if K is None:
+            # no distortion: mvKeysUn == mvKeys and bounds = image rectangle (src/Frame.cc:458-461)
+            return cls(kps, desc, 0.0, float(width), 0.0, float(height), featvec)
+        # UndistortKeyPoints + ComputeImageBounds (src/Frame.cc:403-463)
+        c = _lib.calib(K, distCoef)
+        F = cls(UndistortKeyPoints(kps, K, distCoef), desc, *ComputeImageBounds(width, height, K, distCoef), featvec)
+        F.fx, F.fy, F.cx, F.cy = c.fx, c.fy, c.cx, c.cy
+        F.mvKeysDistorted = kps
+        return F
+
+
+def UndistortKeyPoints(kps, K, distCoef) -> np.ndarray:
+    """Frame::UndistortKeyPoints (src/Frame.cc:403-433): mvKeysUn from mvKeys, on the device
+    (orbx_undistort_keypoints). A bitwise copy when k1 == 0, as the reference's shortcut."""
+    kps = np.ascontiguousarray(kps, KP_DTYPE)
+    out = np.empty(len(kps), KP_DTYPE)
+    c = _lib.calib(K, distCoef)
+    check(lib().orbx_undistort_keypoints(C.byref(c), ptr(kps), len(kps), ptr(out)))
+    return out
+
+
+def ComputeImageBounds(width: int, height: int, K, distCoef) -> tuple:
+    """Frame::ComputeImageBounds (src/Frame.cc:435-463): (mnMinX, mnMaxX, mnMinY, mnMaxY) as
+    float32 values (orbx_image_bounds, host)."""
+    b = GridBounds()
+    c = _lib.calib(K, distCoef)
+    check(lib().orbx_image_bounds(C.byref(c), int(width), int(height), C.byref(b)))
+    return tuple(np.float32(v) for v in (b.min_x, b.max_x, b.min_y, b.max_y))
+
+
+def depth_map_factor(DepthMapFactor: float) -> np.float32:
+    """mDepthMapFactor from the settings file's DepthMapFactor (src/Tracking.cc:150-154)."""
+    f = np.float32(DepthMapFactor)
+    return np.float32(1.0) if abs(float(f)) < 1e-5 else np.float32(1.0) / f
+
+
+def _depth_image(imDepth):
+    """(array, ORBX_DEPTH_*) of a raw depth image; rows and elements at multiples of the element size."""
+    d = np.asarray(imDepth)
+    if d.ndim != 2 or d.dtype not in (np.uint16, np.float32):
+        raise _lib.OrbxError(_lib.ORBX_EINVAL, "imDepth must be a 2-D uint16 or float32 array")
+    if d.size and (d.strides[1] != d.itemsize or d.strides[0] < d.shape[1] * d.itemsize
+                   or d.strides[0] % d.itemsize):
+        d = np.ascontiguousarray(d)
+    return d, (_lib.ORBX_DEPTH_U16 if d.dtype == np.uint16 else _lib.ORBX_DEPTH_F32)
+
+
+def ComputeStereoFromRGBD(kps, kpsUn, imDepth, DepthMapFactor: float, mbf: float):
+    """Frame::ComputeStereoFromRGBD (src/Frame.cc:642-663) on the raw depth image, the convertTo of
+    Tracking::GrabImageRGBD (src/Tracking.cc:276-277) applied to the sampled pixels: returns
+    (mvuRight, mvDepth). The device samples and converts the pixel under every distorted keypoint
+    (orbx_frame_tail_batch); mvuRight = kpsUn.x - mbf / depth is then formed from the caller's
+    undistorted keys, one float32 divide and subtract. ExtractRGBD does all of it on the device."""
+    kps = np.ascontiguousarray(kps, KP_DTYPE)
+    xu = np.ascontiguousarray(np.asarray(kpsUn)["x"], np.float32)
+    n = len(kps)
+    assert len(xu) == n
+    d, dtype = _depth_image(imDepth)
+    if n == 0:
+        return np.zeros(0, np.float32), np.zeros(0, np.float32)
+    h, w = d.shape
+    # no distortion: the kernel's keypoint output is a copy, its depth output is what is read
+    c = _lib.OrbxCalib(1.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0)
+    d = np.ascontiguousarray(d)
+    stride = w * d.itemsize
+    d_img = _lib.DeviceArray(max(d.nbytes, 1))
+    d_img.upload(d)
+    d_in = _lib.DeviceArray(16 + n * 28)
+    d_in.upload(np.array([n], np.int32))
+    d_in.upload(kps, 16)
+    d_un, d_ur, d_dp = _lib.DeviceArray(n * 28), _lib.DeviceArray(n * 4), _lib.DeviceArray(n * 4)
+    check(lib().orbx_frame_tail_batch(
+        C.byref(c), C.c_void_p(d_in.ptr + 16), C.c_void_p(d_in.ptr), n, 1, C.c_void_p(d_img.ptr), dtype,
+        stride * h, stride, w, h, C.c_float(depth_map_factor(DepthMapFactor)), C.c_float(mbf),
+        C.c_void_p(d_un.ptr), C.c_void_p(d_ur.ptr), C.c_void_p(d_dp.ptr), None))
+    depth = d_dp.download(n, np.float32)  # the blocking copy follows the kernel on the null stream
+    with np.errstate(all="ignore"):
+        ok = depth > 0
+        uright = np.where(ok, xu - np.float32(mbf) / np.where(ok, depth, np.float32(1)), np.float32(-1))
+    return uright.astype(np.float32), depth
+
+
+def ExtractRGBD(extractor, imGray, imDepth, K, distCoef, mbf: float, DepthMapFactor: float = 1.0) -> "Frame":
+    """The RGB-D Frame constructor (src/Frame.cc:118-170) up to AssignFeaturesToGrid, with one device
+    round trip (orbx_rgbd_frame): ExtractORB, UndistortKeyPoints and ComputeStereoFromRGBD on the raw
+    depth image (uint16 or float32; DepthMapFactor is the settings file's value), plus
+    ComputeImageBounds. imDepth None: the monocular constructor (:173-227), mvuRight = mvDepth = -1."""
+    img = np.asarray(imGray)
+    c = _lib.calib(K, distCoef)
+    mbf32 = np.float32(mbf)
+    if img.size == 0:
+        kps, desc = extractor(img)
+        kun, uR, dep = kps.copy(), np.zeros(0, np.float32), np.zeros(0, np.float32)
+        height, width = (img.shape + (0, 0))[:2]
+    else:
+        if img.dtype != np.uint8 or img.ndim != 2:
+            raise _lib.OrbxError(_lib.ORBX_EINVAL, "image must be CV_8UC1 (2-D uint8)")
+        if img.strides[1] != 1:
+            img = np.ascontiguousarray(img)
+        height, width = img.shape
+        d, dtype, dptr, dstride = None, _lib.ORBX_DEPTH_U16, None, 0
+        if imDepth is not None:
+            d, dtype = _depth_image(imDepth)
+            if d.shape != img.shape:
+                raise _lib.OrbxError(_lib.ORBX_EINVAL, "imDepth and imGray differ in size")
+            dptr, dstride = ptr(d), d.strides[0]
+        cap = extractor._begin(img)
+        kps, kun = np.empty(cap, KP_DTYPE), np.empty(cap, KP_DTYPE)
+        desc = np.empty((cap, 32), np.uint8)
+        uR, dep = np.empty(cap, np.float32), np.empty(cap, np.float32)
+        n = C.c_int(0)
+        check(lib().orbx_rgbd_frame(
+            extractor.handle, ptr(img), img.strides[0], dptr, dtype, dstride, width, height, C.byref(c),
+            C.c_float(depth_map_factor(DepthMapFactor)), C.c_float(mbf32), ptr(kps), cap, ptr(desc), C.byref(n),
+            ptr(kun), ptr(uR), ptr(dep)))
+        n = n.value
+        kps, kun, desc, uR, dep = kps[:n].copy(), kun[:n].copy(), desc[:n].copy(), uR[:n].copy(), dep[:n].copy()
+    F = Frame(kun, desc, *ComputeImageBounds(width, height, K, distCoef))
+    F.mvKeysDistorted = kps
+    F.mvuRight, F.mvDepth = uR, dep
+    F.fx, F.fy, F.cx, F.cy = c.fx, c.fy, c.cx, c.cy
+    F.mbf = float(mbf32)
+    F.mb = float(mbf32 / np.float32(c.fx))  # src/Frame.cc:167
+    F.mvScaleFactors = np.asarray(extractor.GetScaleFactors(), np.float32)
+    F.mfScaleFactor = extractor.GetScaleFactor()
+    return F
 
 
 def ComputeStereoMatches(F: Frame, extractorLeft, extractorRight, matcher: "ORBmatcher") -> int:

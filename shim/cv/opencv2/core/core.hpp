@@ -1,6 +1,6 @@
 // Minimal OpenCV 3.x core surface for compiling the liborbx shim without
 // OpenCV: only the members ORBextractor.cc / ORBmatcher.cc / Frame touch
-// (cv::Mat of CV_8U or CV_32F elements, cv::KeyPoint, cv::Point2f,
+// (cv::Mat of CV_8U, CV_16U or CV_32F elements, cv::KeyPoint, cv::Point2f,
 // InputArray/OutputArray).
 // Layouts follow OpenCV where the shim relies on them: cv::KeyPoint is
 // pt.x, pt.y, size, angle, response, octave, class_id (28 bytes) and
@@ -16,6 +16,7 @@
 
 #define CV_8U 0
 #define CV_8UC1 0
+#define CV_16U 2
 #define CV_32F 5
 
 typedef unsigned char uchar;
@@ -46,7 +47,7 @@ struct KeyPoint {
       : pt(p), size(s), angle(a), response(r), octave(o), class_id(c) {}
 };
 
-// Single-channel matrix of CV_8U or CV_32F elements with row stride `step`
+// Single-channel matrix of CV_8U, CV_16U (a raw depth image) or CV_32F elements with row stride `step`
 // (bytes); owns its buffer unless it wraps external data (Mat(rows, cols,
 // type, data, step)) or is a row / column view.
 class Mat {
@@ -61,8 +62,8 @@ class Mat {
       : rows(r), cols(c), step(stp ? stp : (size_t)c * esize(type)), data((uchar*)ext), type_(type) {}
 
   static size_t esize(int type) {
-    assert(type == CV_8U || type == CV_32F);
-    return type == CV_32F ? 4 : 1;
+    assert(type == CV_8U || type == CV_16U || type == CV_32F);
+    return type == CV_32F ? 4 : type == CV_16U ? 2 : 1;
   }
   void create(int r, int c, int type) {
     if (buf_ && rows == r && cols == c && type_ == type && step == (size_t)c * esize(type)) return;

@@ -5,8 +5,11 @@
 // mDescriptorsRight, mvuRight, mvDepth), the pose mTcw, mvpMapPoints,
 // mvbOutlier, the scale tables and the static image bounds mnMinX..mnMaxY
 // (Frame.h:110-186). ComputeBoW is src/Frame.cc:394-401; ComputeStereoMatches
-// (:465-639) and isInFrustum (:268-324) are the drop-in bodies in
-// shim/src/Frame.cc. A test stand-in; a
+// (:465-639), isInFrustum (:268-324), UndistortKeyPoints (:403-433),
+// ComputeImageBounds (:435-463) and ComputeStereoFromRGBD (:642-663) are the
+// drop-in bodies in shim/src/Frame.cc; the RGB-D and the calibrated monocular
+// constructor carry the reference's signatures (mK, mDistCoef, mThDepth,
+// mfGridElementWidthInv / HeightInv). A test stand-in; a
 // real build uses the reference's Frame with that one body replaced.
 #ifndef ORBX_SHIM_FRAME_H
 #define ORBX_SHIM_FRAME_H
@@ -84,6 +87,43 @@ class Frame {
     mvpMapPoints.assign(N, static_cast<MapPoint*>(nullptr));
     mvbOutlier.assign(N, false);
   }
+  // Constructor for RGB-D cameras, the reference's signature (src/Frame.cc:118-170).
+  // imDepth is what Tracking::GrabImageRGBD hands over: the reference converts
+  // it first (src/Tracking.cc:276-277); here it may stay raw (CV_16U or
+  // CV_32F) with sDepthMapFactor = Tracking's mDepthMapFactor, and only the
+  // sampled pixels are converted, on the device. Extraction, UndistortKeyPoints
+  // and ComputeStereoFromRGBD are one device round trip (ExtractRGBD,
+  // shim/src/Frame.cc).
+  Frame(const cv::Mat &imGray, const cv::Mat &imDepth, const double &timeStamp, ORBextractor* extractor,
+        ORBVocabulary* voc, cv::Mat &K, cv::Mat &distCoef, const float &bf, const float &thDepth)
+      : mpORBvocabulary(voc), mpORBextractorLeft(extractor), mTimeStamp(timeStamp), mK(K.clone()),
+        mDistCoef(distCoef.clone()), mbf(bf), mThDepth(thDepth) {
+    scale_info();
+    ExtractRGBD(imGray, imDepth);
+    finish_calibrated(imGray, K);
+  }
+  // Constructor for Monocular cameras, the reference's signature (src/Frame.cc:173-227)
+  Frame(const cv::Mat &imGray, const double &timeStamp, ORBextractor* extractor, ORBVocabulary* voc, cv::Mat &K,
+        cv::Mat &distCoef, const float &bf, const float &thDepth)
+      : mpORBvocabulary(voc), mpORBextractorLeft(extractor), mTimeStamp(timeStamp), mK(K.clone()),
+        mDistCoef(distCoef.clone()), mbf(bf), mThDepth(thDepth) {
+    scale_info();
+    ExtractRGBD(imGray, cv::Mat());  // no depth: mvuRight = mvDepth = -1 (:200-201)
+    finish_calibrated(imGray, K);
+  }
+  // Undistort keypoints given OpenCV distortion parameters; a copy when k1 == 0
+  // (src/Frame.cc:403-433; shim/src/Frame.cc over orbx_undistort_keypoints)
+  void UndistortKeyPoints();
+  // Computes image bounds for the undistorted image (:435-463, orbx_image_bounds)
+  void ComputeImageBounds(const cv::Mat &imLeft);
+  // Associate a "right" coordinate to a keypoint if there is valid depth in the
+  // depthmap (:642-663). imDepth raw or converted, as for the RGB-D constructor.
+  void ComputeStereoFromRGBD(const cv::Mat &imDepth);
+  // The RGB-D constructor's ExtractORB + UndistortKeyPoints +
+  // ComputeStereoFromRGBD (:134-144) in one call (orbx_rgbd_frame): mvKeys,
+  // mDescriptors, N, mvKeysUn, mvuRight, mvDepth
+  void ExtractRGBD(const cv::Mat &imGray, const cv::Mat &imDepth);
+
   void ComputeBoW() {
     if (mBowVec.empty()) {
       std::vector<cv::Mat> vCurrentDesc;  // Converter::toDescriptorVector
@@ -109,8 +149,19 @@ class Frame {
   ORBVocabulary* mpORBvocabulary = nullptr;
   ORBextractor* mpORBextractorLeft = nullptr;
   ORBextractor* mpORBextractorRight = nullptr;
+  double mTimeStamp = 0.0;
+  // Calibration matrix and OpenCV distortion parameters (Frame.h:110-118)
+  cv::Mat mK;
+  cv::Mat mDistCoef;
   static float fx, fy, cx, cy, invfx, invfy;
   float mbf = 0.f, mb = 0.f;
+  // Threshold close/far points (Frame.h:127-129)
+  float mThDepth = 0.f;
+  static float mfGridElementWidthInv, mfGridElementHeightInv;
+  static bool mbInitialComputations;
+  // mDepthMapFactor of Tracking (src/Tracking.cc:150-154) for a depth image
+  // handed over raw; 1 = imDepth is CV_32F and already converted
+  static float sDepthMapFactor;
   int N = 0;
   long unsigned int mnId = 0;
   std::vector<cv::KeyPoint> mvKeys, mvKeysRight, mvKeysUn;
@@ -135,6 +186,36 @@ class Frame {
     mvInvScaleFactors = mpORBextractorLeft->GetInverseScaleFactors();
     mvLevelSigma2 = mpORBextractorLeft->GetScaleSigmaSquares();
     mvInvLevelSigma2 = mpORBextractorLeft->GetInverseScaleSigmaSquares();
+  }
+  // the calibrated constructors after their extraction (src/Frame.cc:137-169)
+  void finish_calibrated(const cv::Mat& imGray, const cv::Mat& K) {
+    if (mvKeys.empty()) return;
+    mvpMapPoints.assign(N, static_cast<MapPoint*>(nullptr));
+    mvbOutlier.assign(N, false);
+    // This is done only for the first Frame (or after a change in the calibration)
+    if (mbInitialComputations) {
+      ComputeImageBounds(imGray);
+      mfGridElementWidthInv = 64.f / (mnMaxX - mnMinX);   // FRAME_GRID_COLS
+      mfGridElementHeightInv = 48.f / (mnMaxY - mnMinY);  // FRAME_GRID_ROWS
+      fx = K.at<float>(0, 0);
+      fy = K.at<float>(1, 1);
+      cx = K.at<float>(0, 2);
+      cy = K.at<float>(1, 2);
+      invfx = 1.0f / fx;
+      invfy = 1.0f / fy;
+      mbInitialComputations = false;
+    }
+    mb = mbf / fx;
+  }
+  orbx_calib calib() const {
+    orbx_calib c{mK.at<float>(0, 0), mK.at<float>(1, 1), mK.at<float>(0, 2), mK.at<float>(1, 2), 0, 0, 0, 0, 0};
+    const int nd = mDistCoef.rows * mDistCoef.cols;
+    c.k1 = mDistCoef.at<float>(0);
+    c.k2 = mDistCoef.at<float>(1);
+    c.p1 = mDistCoef.at<float>(2);
+    c.p2 = mDistCoef.at<float>(3);
+    c.k3 = nd > 4 ? mDistCoef.at<float>(4) : 0.f;
+    return c;
   }
   static void image_bounds(const cv::Mat& im) {
     mnMinX = 0.0f;

@@ -13,7 +13,10 @@
 //                                 (stereo Frames, two extraction threads each, + ComputeStereoMatches)
 //   orbx_shim_driver --latency MONO.u8 LEFT.u8 RIGHT.u8 NFRAMES W H NCALLS WARM
 //                                 (per-call host times of the drop-in path, one JSON line)
+//   orbx_shim_driver --rgbd GRAY.u8 DEPTH.raw u16|f32 W H NFEATURES fx,fy,cx,cy,k1,k2,p1,p2[,k3] BF DEPTHMAPFACTOR OUTDIR
+//                                 (one RGB-D Frame from a gray image and its raw depth image)
 #include <algorithm>
+#include <cmath>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -98,6 +101,67 @@ static bool read_file(const char* path, std::vector<uint8_t>& v) {
   if (f) fclose(f);
   if (!ok) fprintf(stderr, "cannot read %s\n", path);
   return ok;
+}
+
+// The RGB-D Frame constructor (src/Frame.cc:118-170) on one gray image and its
+// raw depth image (u16 or f32, as the dataset stores it), as Tracking::GrabImageRGBD
+// would build it with mDepthMapFactor = 1 / DEPTHMAPFACTOR (src/Tracking.cc:150-154)
+// and the conversion left to the Frame. Writes mvKeys, mDescriptors, mvKeysUn,
+// mvuRight, mvDepth and the four bounds; then the same members from the three
+// drop-in bodies called one by one on a monocular Frame of the same image
+// (UndistortKeyPoints, ComputeStereoFromRGBD), suffixed _steps.
+static int run_rgbd(const char* gray, const char* depth, const std::string& dtype, int W, int H, int nfeatures,
+                    const char* calib, float bf, float depth_map_factor, const std::string& out) {
+  if (dtype != "u16" && dtype != "f32") {
+    fprintf(stderr, "--rgbd: DEPTHTYPE must be u16 or f32\n");
+    return 1;
+  }
+  float c[9] = {};
+  if (sscanf(calib, "%f,%f,%f,%f,%f,%f,%f,%f,%f", c, c + 1, c + 2, c + 3, c + 4, c + 5, c + 6, c + 7, c + 8) < 8) {
+    fprintf(stderr, "--rgbd: CALIB is fx,fy,cx,cy,k1,k2,p1,p2[,k3]\n");
+    return 1;
+  }
+  const size_t es = dtype == "u16" ? 2 : 4;
+  std::vector<uint8_t> G((size_t)W * H), D((size_t)W * H * es);
+  if (!read_file(gray, G) || !read_file(depth, D)) return 2;
+  cv::Mat K(3, 3, CV_32F), dist(1, 5, CV_32F);
+  for (int i = 0; i < 9; ++i) K.at<float>(i / 3, i % 3) = (i % 4 == 0) ? 1.f : 0.f;
+  K.at<float>(0, 0) = c[0];
+  K.at<float>(1, 1) = c[1];
+  K.at<float>(0, 2) = c[2];
+  K.at<float>(1, 2) = c[3];
+  for (int i = 0; i < 5; ++i) dist.at<float>(i) = c[4 + i];
+  // src/Tracking.cc:150-154
+  float factor = depth_map_factor;
+  if (fabs(factor) < 1e-5)
+    factor = 1;
+  else
+    factor = 1.0f / factor;
+  Frame::sDepthMapFactor = factor;
+  ORBextractor extractor(nfeatures, 1.2f, 8, 20, 7, W, H);
+  const cv::Mat imGray(H, W, CV_8U, G.data(), W), imDepth(H, W, dtype == "u16" ? CV_16U : CV_32F, D.data(), W * es);
+  const float thDepth = 40.f;
+  auto dump = [&](Frame& F, const std::string& sfx) {
+    write_file(out + "/keys" + sfx + ".bin", F.mvKeys.data(), F.mvKeys.size() * sizeof(cv::KeyPoint));
+    write_file(out + "/keysun" + sfx + ".bin", F.mvKeysUn.data(), F.mvKeysUn.size() * sizeof(cv::KeyPoint));
+    write_file(out + "/desc" + sfx + ".bin", F.mDescriptors.data, (size_t)F.N * 32);
+    write_file(out + "/uright" + sfx + ".bin", F.mvuRight.data(), F.mvuRight.size() * 4);
+    write_file(out + "/depth" + sfx + ".bin", F.mvDepth.data(), F.mvDepth.size() * 4);
+    const float b[7] = {Frame::mnMinX, Frame::mnMaxX, Frame::mnMinY, Frame::mnMaxY, F.mb,
+                        Frame::mfGridElementWidthInv, Frame::mfGridElementHeightInv};
+    write_file(out + "/bounds" + sfx + ".bin", b, sizeof b);
+  };
+  Frame F(imGray, imDepth, 0.0, &extractor, nullptr, K, dist, bf, thDepth);
+  dump(F, "");
+  Frame::mbInitialComputations = true;
+  Frame M(imGray, 0.0, &extractor, nullptr, K, dist, bf, thDepth);
+  for (float v : M.mvuRight)
+    if (v != -1.f) throw std::runtime_error("monocular Frame with stereo information");
+  M.mvKeysUn.clear();
+  M.UndistortKeyPoints();
+  M.ComputeStereoFromRGBD(imDepth);
+  dump(M, "_steps");
+  return 0;
 }
 
 // median / p99 of per-call times (ms) as a JSON object
@@ -279,12 +343,19 @@ int main(int argc, char** argv) {
                          atoi(argv[9]));
     if (argc == 9 && std::string(argv[1]) == "--stereo")
       return run_stereo(argv[2], argv[3], atoi(argv[4]), atoi(argv[5]), atoi(argv[6]), (float)atof(argv[7]), argv[8]);
+    if (argc == 12 && std::string(argv[1]) == "--rgbd")
+      return run_rgbd(argv[2], argv[3], argv[4], atoi(argv[5]), atoi(argv[6]), atoi(argv[7]), argv[8],
+                      (float)atof(argv[9]), (float)atof(argv[10]), argv[11]);
   } catch (const std::exception& e) {
     fprintf(stderr, "error: %s\n", e.what());
     return 4;
   }
   if (argc != 7) {
-    fprintf(stderr, "usage: %s FRAMES.u8 NFRAMES W H VOC.txt|- OUTDIR\n", argv[0]);
+    fprintf(stderr,
+            "usage: %s FRAMES.u8 NFRAMES W H VOC.txt|- OUTDIR\n"
+            "       %s --rgbd GRAY.u8 DEPTH.raw u16|f32 W H NFEATURES fx,fy,cx,cy,k1,k2,p1,p2[,k3] BF DEPTHMAPFACTOR "
+            "OUTDIR\n",
+            argv[0], argv[0]);
     return 1;
   }
   const std::string out = argv[6];

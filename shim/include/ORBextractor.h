@@ -68,6 +68,16 @@ class ORBextractor {
                             cv::OutputArray descLeft, std::vector<cv::KeyPoint>& keysRight, cv::OutputArray descRight,
                             std::vector<float>& uRight, std::vector<float>& depth);
 
+  // The RGB-D Frame's ExtractORB, UndistortKeyPoints and ComputeStereoFromRGBD
+  // (src/Frame.cc:134-144) with one device round trip (orbx_rgbd_frame):
+  // imDepth is the raw depth image (CV_16U or CV_32F) and depthMapFactor the
+  // multiplier Tracking::GrabImageRGBD would convert it with (mDepthMapFactor;
+  // 1 for a CV_32F image it converted already). An empty imDepth gives the
+  // monocular constructor's steps (:189-201), uRight = depth = -1.
+  void ExtractRGBD(const cv::Mat& imGray, const cv::Mat& imDepth, const orbx_calib& calib, float depthMapFactor,
+                   float mbf, std::vector<cv::KeyPoint>& keys, cv::OutputArray descriptors,
+                   std::vector<cv::KeyPoint>& keysUn, std::vector<float>& uRight, std::vector<float>& depth);
+
   int inline GetLevels() { return nlevels; }
   float inline GetScaleFactor() { return (float)scaleFactor; }
   std::vector<float> inline GetScaleFactors() { return mvScaleFactor; }

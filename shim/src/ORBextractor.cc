@@ -209,6 +209,45 @@ void ORBextractor::ExtractStereo(ORBextractor& left, ORBextractor& right, const 
   }
 }
 
+void ORBextractor::ExtractRGBD(const cv::Mat& imGray, const cv::Mat& imDepth, const orbx_calib& calib,
+                               float depthMapFactor, float mbf, std::vector<cv::KeyPoint>& keys,
+                               cv::OutputArray descriptors, std::vector<cv::KeyPoint>& keysUn,
+                               std::vector<float>& uRight, std::vector<float>& depth) {
+  keysUn.clear();
+  uRight.clear();
+  depth.clear();
+  if (imGray.empty()) {  // no outputs, as operator()
+    (*this)(imGray, cv::noArray(), keys, descriptors);
+    return;
+  }
+  assert(imGray.type() == CV_8UC1);
+  const bool has_depth = !imDepth.empty();
+  if (has_depth && imDepth.type() != CV_16U && imDepth.type() != CV_32F)
+    throw std::runtime_error("liborbx: the depth image must be CV_16U or CV_32F");
+  if (has_depth && (imDepth.rows != imGray.rows || imDepth.cols != imGray.cols))
+    throw std::runtime_error("liborbx: the depth image's size differs from the gray image's");
+  const auto start = std::chrono::steady_clock::now();
+  {
+    GetTime total(this, "Total Time ORB extraction", -1);
+    BeginCall(imGray, keys, descriptors);
+    keysUn.resize(cap_);
+    uRight.resize(cap_);
+    depth.resize(cap_);
+    int n = 0;
+    orbx_check(orbx_rgbd_frame(h_, imGray.data, imGray.step, has_depth ? imDepth.data : nullptr,
+                               has_depth && imDepth.type() == CV_32F ? ORBX_DEPTH_F32 : ORBX_DEPTH_U16,
+                               has_depth ? imDepth.step : 0, imGray.cols, imGray.rows, &calib, depthMapFactor, mbf,
+                               reinterpret_cast<orbx_kp*>(keys.data()), cap_, descriptors.getMatRef().data, &n,
+                               reinterpret_cast<orbx_kp*>(keysUn.data()), uRight.data(), depth.data()));
+    keysUn.resize(n);
+    uRight.resize(n);
+    depth.resize(n);
+    EndCall(n, keys, descriptors);
+  }
+  totalTime += std::chrono::duration<long long, std::nano>(std::chrono::steady_clock::now() - start).count();
+  nFrame++;
+}
+
 GetTime::GetTime(std::vector<times_t>& times, int nFrame, std::string name, int level) : o(nullptr), times(times) {
   t.frame = nFrame;
   t.name = name;
