@@ -10,13 +10,18 @@
 //
 // Two keypoints per wavefront, 32 lanes each. Every global access of a
 // keypoint is issued in one burst after its key is known: the 31 rows of the
-// IC patch (lane = patch column, one byte load per row, coalesced across the
-// lanes) and the 39 x 64-byte blurred patch that the rotated BRIEF pattern
-// can reach (radius <= 19), staged in LDS with 16-byte loads. Moments are
+// IC patch (12-byte pieces, three per row, loaded straight into the wave's
+// LDS patch areas, where lane = patch row reads its row back; on a level 0
+// whose rows are not 16-byte aligned each lane loads its own row instead)
+// and the 39 x 64-byte blurred patch that the rotated BRIEF pattern can
+// reach (radius <= 19), staged in LDS with 16-byte loads. Moments are
 // reduced across the 32 lanes with DPP, cv::fastAtan2 and glibc sin/cos are
 // evaluated per lane, and 8 tests per lane (test t = lane + 32k) give, by
 // one ballot per k, descriptor dword k of both keypoints at once
 // (bit j of byte i = test 8i + j).
+#if defined(ORBX_OB_IC_SAMELINE) && !defined(ORBX_DIAG)
+#error "result-changing diagnostic switches need -DORBX_DIAG"
+#endif
 #include <atomic>
 #include <mutex>
 
@@ -73,9 +78,28 @@ __device__ __forceinline__ int half_sum(int v) {
   return (threadIdx.x & 32) ? hi : lo;
 }
 
+// IC rows through LDS: a half-wave's 31 rows x 36 bytes (the 9 dwords from the
+// dword boundary below x - 15) as 93 pieces of 12 bytes, piece i = 3 * row +
+// third, loaded by lane i % 32 in load i / 32 straight into LDS
+// (buffer_load_dwordx3 ... lds). Such a load writes lane j's 12 bytes at the
+// wave's base + 16 j (a 16-byte slot each, its last dword untouched:
+// measured), so load k of half h lands at k * kIcLoadBytes + h *
+// kIcHalfBytes + 16 * (i % 32). Lane = row reads its three pieces back as
+// three 12-byte reads, slot (3 * row + third) % 32 of load (3 * row + third)
+// / 32: the 8 lanes of every lane group of a ds_read_b96 ({0-3, 20-23},
+// {4-7, 16-19}, ...; the 16 of a ds_read_b128 likewise) are rows all
+// different mod 8 (mod 16), so are their slots (3 is odd), and the reads
+// share no bank. The two halves' rows take 3 KB of the wave's two patch areas.
+constexpr int kIcPieces = kPatchSize * 3, kIcLoads = (kIcPieces + 31) / 32;
+constexpr int kIcHalfBytes = 32 * 16, kIcLoadBytes = 64 * 16;
+static_assert(kIcLoads * kIcLoadBytes <= 2 * kObRows * kObStride, "the IC rows of a wave fit its two patch areas");
+static_assert((kIcHalfBytes / 4) % 64 == 0 && (kIcLoadBytes / 4) % 64 == 0, "halves and loads start on bank 0");
+
 // kLv: the level loops' unrolled length (8 covers the usual 8-level
-// pyramid in half the scalar bookkeeping of kMaxLevels)
-template <int kLv>
+// pyramid in half the scalar bookkeeping of kMaxLevels). kRows0: level 0's
+// rows are not 16-byte aligned (or too far apart for a 32-bit offset), so
+// its workgroups load the IC rows lane = row.
+template <int kLv, bool kRows0>
 __global__ __launch_bounds__(kObThreads) void orient_brief_kernel(ExtractParams P, LevelPtrs lp,
                                                                   const uint8_t* __restrict__ blur,
                                                                   const uint32_t* __restrict__ qkeys,
@@ -153,14 +177,56 @@ __global__ __launch_bounds__(kObThreads) void orient_brief_kernel(ExtractParams 
   // an empty slot works on a dummy keypoint at the level centre (never stored)
   const int x = valid ? key_x(key) + g_minBX : g_w / 2, y = valid ? key_y(key) + g_minBY : g_h / 2;
 
-  // ---- one burst of loads: blurred patch (16-byte chunks, five per lane) and
-  // IC rows (lane v - 15 = patch row: the row's 31 pixels within 9 dwords from
-  // the dword boundary below x - 15; they reach at most byte x + 20 <= w of a
-  // row <= h - 5, so they stay inside the level). Every load is unconditional
-  // (an empty slot reads around its dummy keypoint, the IC rows the level
-  // start) so that no branch join waits for them.
+  // ---- one burst of loads: the IC rows and the blurred patch (16-byte
+  // chunks, five per lane). Every load is unconditional (an empty slot reads
+  // around its dummy keypoint at the level centre) so that no branch join
+  // waits for them.
   const int c0 = (x - kObRadius) & ~15;
   const int pitch = lpitch;
+#ifdef ORBX_OB_IC_SAMELINE  // diagnostics (tools/variant.sh): lane = row loads, every lane at the level start
+  constexpr bool ic_rows = true;
+#else
+  const bool ic_rows = kRows0 && l == 0;  // uniform
+#endif
+  // IC rows. The pixels x - 15 .. x + 15 of a row lie within 9 dwords from
+  // the dword boundary below x - 15; those reach at most byte x + 20 <= w of
+  // a row <= h - 5, so both paths stay inside the level.
+  uint8_t* const icw = s_patch[hk & ~1];  // the wave's IC rows (both halves'), dead before the blurred patch is written
+  uint32_t w[9];
+  int sh;
+  if (ic_rows) {
+    // lane v - 15 = patch row, 9 dwords of its own row; an empty slot reads the level start
+    const uint8_t* rp = lbase + f * lfstride + (long long)(y - kHalfPatch + min(lane, kPatchSize - 1)) * pitch +
+                        (x - kHalfPatch);
+#ifdef ORBX_OB_IC_SAMELINE
+    const uint32_t* q = (const uint32_t*)lbase;
+#else
+    const uint32_t* q = valid ? (const uint32_t*)((uintptr_t)rp & ~(uintptr_t)3) : (const uint32_t*)lbase;
+#endif
+    sh = (int)((uintptr_t)rp & 3);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) w[k] = q[k];
+  } else {
+    // 16-byte aligned rows (every level >= 1; level 0 by the launch's check):
+    // the row's dword boundary below x - 15 is column (x - 15) & ~3. Pieces
+    // (kIcPieces above) straight into LDS through a descriptor over the
+    // frame's level plane: rows (h - 1) * pitch + ceil16(w) bytes, what the
+    // caller guarantees readable of level 0 (orbx_c.h) and no more than h *
+    // pitch of a level >= 1 (64-byte pitches). The three pieces past the 93
+    // are row y + 16, which lies in the level (or reads 0 past its end) and
+    // lands behind the rows that are read back.
+    const __amdgpu_buffer_rsrc_t irs = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)(lbase + f * lfstride), (short)0, (g_h - 1) * pitch + ((g_w + 15) & ~15), 0x00020000);
+    const int ic0 = (y - kHalfPatch) * pitch + ((x - kHalfPatch) & ~3);
+#pragma unroll
+    for (int k = 0; k < kIcLoads; ++k) {
+      const int i = lane + 32 * k, r = i / 3;
+      typedef __attribute__((address_space(3))) void lds_void;
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(irs, (lds_void*)(uintptr_t)(icw + k * kIcLoadBytes), 12,
+                                               ic0 + r * pitch + (i - 3 * r) * 12, 0, 0, 0);
+    }
+    sh = (x - kHalfPatch) & 3;
+  }
   constexpr int kChunks = kObRows * 4, kPerLane = (kChunks + 31) / 32;
   uint4 pv[kPerLane];
   // lane -> (row lane / 4 of an 8-row block, chunk lane % 4): load k is row
@@ -179,13 +245,6 @@ __global__ __launch_bounds__(kObThreads) void orient_brief_kernel(ExtractParams 
     const u32x4 t = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(prs, pvoff + 8 * k * g_pitch, 0, 0));
     pv[k] = make_uint4(t.x, t.y, t.z, t.w);
   }
-  const uint8_t* rp = lbase + f * lfstride + (long long)(y - kHalfPatch + min(lane, kPatchSize - 1)) * pitch +
-                      (x - kHalfPatch);
-  const uint32_t* q = valid ? (const uint32_t*)((uintptr_t)rp & ~(uintptr_t)3) : (const uint32_t*)lbase;
-  const int sh = (int)((uintptr_t)rp & 3);
-  uint32_t w[9];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) w[k] = q[k];
 #pragma unroll
   for (int k = 0; k < kTestsPer; ++k)
     if (tid + k * kObThreads < 256) s_tests[tid + k * kObThreads] = test_v[k];
@@ -198,7 +257,7 @@ __global__ __launch_bounds__(kObThreads) void orient_brief_kernel(ExtractParams 
   if (tid < kSincosDoubles) ((double*)s_sincos)[tid] = sincos_v;
   // an empty slot writes its own unused patch; the loads hold row
   // (lane / 4) + 8k, and the rows past the patch are not stored
-  {
+  auto stage_patch = [&] {
     uint8_t* dst = s_patch[hk];
 #pragma unroll
     for (int k = 0; k < kPerLane; ++k) {
@@ -211,8 +270,22 @@ __global__ __launch_bounds__(kObThreads) void orient_brief_kernel(ExtractParams 
         *(uint2*)(dst + r * kObStride + ch * 16 + 8) = make_uint2(pv[k].z, pv[k].w);
       }
     }
+  };
+  if (ic_rows) stage_patch();
+  __syncthreads();  // IC rows or staged patch, test table, IC coefficient table, sincosf tables
+  if (!ic_rows) {
+    // lane = patch row reads its 9 dwords back: piece 3 * row + t is slot
+    // piece % 32 of load piece / 32 (conflict-free, kIcPieces above)
+    const uint8_t* ich = icw + (hk & 1) * kIcHalfBytes;
+#pragma unroll
+    for (int t = 0; t < 3; ++t) {
+      const int i = 3 * min(lane, kPatchSize - 1) + t;
+      const uint4 p = *(const uint4*)(ich + (i >> 5) * kIcLoadBytes + (i & 31) * 16);
+      w[3 * t] = p.x;
+      w[3 * t + 1] = p.y;
+      w[3 * t + 2] = p.z;
+    }
   }
-  __syncthreads();  // staged patch, test table, IC coefficient table, sincosf tables
 
   // ---- IC_Angle (:164-191): per row, the pixels weighted with v_dot4_u32_u8
   // against coefficient dwords (u for u > 0 / -u for u < 0 / 1, inside the
@@ -231,6 +304,13 @@ __global__ __launch_bounds__(kObThreads) void orient_brief_kernel(ExtractParams 
     }
     m10 = (int)pos - (int)neg;
     m01 = v * (int)sum;
+  }
+  if (!ic_rows) {
+    // the blurred patch over the IC rows: both are this wave's alone, and a
+    // wave's LDS accesses complete in order, so the row reads above are
+    // served before these stores; no workgroup barrier
+    __builtin_amdgcn_wave_barrier();
+    stage_patch();
   }
   m10 = half_sum(m10);
   m01 = half_sum(m01);
@@ -339,12 +419,25 @@ int launch_orient_brief(const ExtractParams& P, const LevelPtrs& lp, const Extra
     }
   }
   dim3 grid((P.kp_per_frame + kObKps - 1) / kObKps, batch);
+  // Level 0's IC rows go through LDS in 12-byte pieces when its rows are
+  // 16-byte aligned and every offset (y + 16) * pitch + x + 21 of the piece
+  // loads fits 31 bits; the caller's frames otherwise take the lane = row
+  // loads. Levels >= 1 (64-byte pitches, planes of at most 4096 rows) always
+  // qualify: static_assert below.
+  static_assert((long long)(kMaxLevelDim + 1) * (kMaxLevelDim + 64) <= INT_MAX, "a level plane's offsets fit 31 bits");
+#ifdef ORBX_OB_IC_SAMELINE
+  const bool rows0 = true;
+#else
+  const bool rows0 = !lp.aligned16[0] || (long long)(P.lv[0].h + 1) * lp.pitch[0] + P.lv[0].w + 16 > INT_MAX;
+#endif
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, dim3(kObThreads), 0, s, P, lp, X.blur, X.qkeys, X.qcounts, X.umax, kps, desc,
+                       counts);
+  };
   if (P.L <= 8)
-    hipLaunchKernelGGL(orient_brief_kernel<8>, grid, dim3(kObThreads), 0, s, P, lp, X.blur, X.qkeys, X.qcounts,
-                       X.umax, kps, desc, counts);
+    rows0 ? launch(orient_brief_kernel<8, true>) : launch(orient_brief_kernel<8, false>);
   else
-    hipLaunchKernelGGL(orient_brief_kernel<kMaxLevels>, grid, dim3(kObThreads), 0, s, P, lp, X.blur, X.qkeys,
-                       X.qcounts, X.umax, kps, desc, counts);
+    rows0 ? launch(orient_brief_kernel<kMaxLevels, true>) : launch(orient_brief_kernel<kMaxLevels, false>);
   return hipGetLastError() == hipSuccess ? ORBX_OK : ORBX_EDEVICE;
 }
 
