@@ -102,6 +102,7 @@ struct DeviceBuf {
 
 struct Plan {
   int W = 0, H = 0, B = 0;
+  long long level_bytes = 0;  // the planes of every level of B frames (pyramid and blur buffers)
   ExtractParams P{};
   std::vector<CellGeom> cells;
   std::vector<int2> rtab;
@@ -341,6 +342,58 @@ static bool plan_pyr_cols(const ExtractParams& P, const std::vector<int2>& rtab,
   return true;
 }
 
+// The bounds of plan q's column records (written by plan_band_pyramid, read by
+// pyr_band_kernel) as code: every record lies inside the table at a 16-byte
+// boundary; a run's dword pair starts at a multiple of 4 inside the source
+// level's LDS row or at most 8 bytes past its pitch (a thread's runs end up to
+// 6 columns past the tile's computed ones, at most 12 source columns at scale
+// 2, and a row pitch holds 9 spare bytes, level 0's 1), so that its 8 bytes end
+// at most 16 past the row: in the next row, or in the 16 spare bytes that end
+// the kernel's LDS block; a selector picks
+// bytes 0..7 of the pair; and a run flagged for a store lies inside the tile's
+// owned columns, which lie inside the level; and the bands' row entries (below).
+// plan_band_pyramid refuses a plan
+// that fails (the per-level kernel runs instead). Returns the records checked,
+// or -1.
+static long long pyr_records_ok(const ExtractParams& P, const std::vector<int2>& rtab,
+                                const ExtractParams::PyrPlan& q) {
+  const int L = P.L;
+  long long n = 0;
+  // a band's staged row entries: inside the table, one per computed row of
+  // levels 1 .. L-1, within the LDS bytes the plan sets aside for them
+  for (int b = 0; b < q.nbands; ++b) {
+    const int2* bt = rtab.data() + q.bands + (long long)b * L * 2;
+    long long rows = 0;
+    for (int l = 1; l < L; ++l) rows += bt[2 * l].y - bt[2 * l].x + 1;
+    const int2 yh = bt[1];
+    if (yh.x <= 0 || yh.y != rows || (long long)yh.x + yh.y > (long long)rtab.size() || rows * 8 > q.lds_y) return -1;
+  }
+  for (int t = 0; t < q.nct; ++t)
+    for (int l = 1; l < L; ++l) {
+      const int2* xt = rtab.data() + q.ctiles + ((long long)t * L + l) * 4;
+      const int2 xc = xt[0], xo = xt[1], sp = xt[-4 + 2];
+      const int G = (xc.y - xc.x + 1 + 7) >> 3;
+      const long long at = xt[3].x;
+      if (at <= 0 || (at & 1) || at + 12LL * G > (long long)rtab.size()) return -1;
+      if (xo.x < 0 || xo.y >= P.lv[l].w || xo.x > xo.y) return -1;
+      for (int gi = 0; gi < G; ++gi, ++n) {
+        const uint32_t* rec = (const uint32_t*)(rtab.data() + at + 12LL * gi);
+        for (int k = 0; k < 4; ++k) {
+          const int off = (int)rec[k], gx = xc.x + 2 * (gi + k * G);
+          if (off < 0 || (off & 3) || off > sp.x + 8) return -1;
+          for (int j = 0; j < 2; ++j) {
+            const uint32_t sel = rec[4 + 2 * k + j], o = sel & 0xFF;
+            if (sel != (0x0c000c00u | o | ((o + 1) << 16)) || o > 6) return -1;
+          }
+          if (((rec[20] >> k) & 1) && (gx < xo.x || gx + 1 > xo.y)) return -1;
+          if (((rec[20] >> (4 + k)) & 1) && gx != xo.y) return -1;
+        }
+        if (rec[20] >> 8) return -1;
+      }
+    }
+  return n;
+}
+
 static void plan_band_pyramid(ExtractParams& P, std::vector<int2>& rtab) {
   P.pyr_fused = 0;
   const int L = P.L;
@@ -478,16 +531,69 @@ static void plan_band_pyramid(ExtractParams& P, std::vector<int2>& rtab) {
         rtab.push_back(make_int2(c.lo[b * L + l], c.chi[b * L + l]));
         rtab.push_back(make_int2(c.lo[b * L + l], c.ohi[b * L + l]));
       }
+    // Per band, the row entries pyr_band_kernel stages in LDS: the computed
+    // rows of levels 1 .. L-1 in turn, {sy0 | sy1 << 16, 4*b0 | 4*b1 << 16}
+    // (the 2x2 area mean: rows 2r and 2r + 1, 4*b = 2048). The band's level-0
+    // own entry, which nothing reads, becomes {the list's offset, its length}.
+    for (int b = 0; b < c.nb; ++b) {
+      const int at = (int)rtab.size();
+      for (int l = 1; l < L; ++l)
+        for (int r = c.lo[b * L + l]; r <= c.chi[b * L + l]; ++r) {
+          const int2 e = rtab[P.lv[l].ytab + r];
+          rtab.push_back(P.lv[l].area2x ? make_int2((2 * r) | ((2 * r + 1) << 16), 2048 | (2048 << 16))
+                                        : make_int2(e.x, e.y << 2));
+        }
+      rtab[q.bands + b * L * 2 + 1] = make_int2(at, (int)rtab.size() - at);
+    }
     q.ctiles = (int)rtab.size();
     const PyrCols& C = c.cols;
+    auto origin = [&](int t, int l) { return l == 0 ? (C.lo[t * L] & ~15) : C.lo[t * L + l]; };
     for (int t = 0; t < C.nct; ++t)
       for (int l = 0; l < L; ++l) {
         const int lo = C.lo[t * L + l];
         rtab.push_back(make_int2(lo, C.chi[t * L + l]));
         rtab.push_back(make_int2(lo, C.ohi[t * L + l]));
-        rtab.push_back(make_int2(C.lpitch[l], l == 0 ? (lo & ~15) : lo));
+        rtab.push_back(make_int2(C.lpitch[l], origin(t, l)));
+        rtab.push_back(make_int2(0, 0));  // .x: the level's column records (below)
       }
+    // Column records of pyr_band_kernel, per (tile, level >= 1, column group
+    // gi): what a thread's 8 columns need in the row loop, ready for its
+    // registers: 24 dwords = the 4 runs' LDS-relative dword-pair offsets, the
+    // 8 v_perm_b32 selectors, the 8 {a0 | a1 << 16}, and the store flags (bit
+    // k: run k is owned whole by the tile; bit 4 + k: only its first column
+    // is, the level's last). None of it depends on the frame, the band or the
+    // launch, and worked out per thread and level in the kernel it was the
+    // largest share of the kernel's vector instructions.
+    // Records start at even int2 indices: 16-byte loads.
+    for (int t = 0; t < C.nct; ++t)
+      for (int l = 1; l < L; ++l) {
+        if (rtab.size() & 1) rtab.push_back(make_int2(0, 0));
+        rtab[q.ctiles + (t * L + l) * 4 + 3].x = (int)rtab.size();
+        const LevelGeom& g = P.lv[l];
+        const int lo = C.lo[t * L + l], ohi = C.ohi[t * L + l];
+        const int G = (C.chi[t * L + l] - lo + 1 + 7) >> 3, org = origin(t, l - 1);
+        for (int gi = 0; gi < G; ++gi) {
+          uint32_t rec[24] = {};
+          for (int qq = 0; qq < 8; ++qq) {
+            const int col = lo + 2 * (gi + (qq >> 1) * G) + (qq & 1);  // pyr_col
+            const int2 e = rtab[g.xtab2 + std::min(col, g.w - 1)];
+            const int sx = e.x - org;
+            if (!(qq & 1)) rec[qq >> 1] = (uint32_t)(sx & ~3);
+            const uint32_t o = (uint32_t)sx - rec[qq >> 1];  // 0 .. 6
+            rec[4 + qq] = 0x0c000c00u | o | ((o + 1) << 16);
+            rec[12 + qq] = g.area2x ? (2048u | (2048u << 16)) : (uint32_t)e.y;
+          }
+          for (int k = 0; k < 4; ++k) {
+            const int gx = lo + 2 * (gi + k * G);
+            if (gx >= lo && gx < ohi) rec[20] |= 1u << k;
+            if (gx == ohi) rec[20] |= 16u << k;
+          }
+          for (int i = 0; i < 24; i += 2) rtab.push_back(make_int2((int)rec[i], (int)rec[i + 1]));
+        }
+      }
+    if (pyr_records_ok(P, rtab, q) < 0) --P.pyr_nplans;
   }
+  if (!P.pyr_nplans) return;
   P.pyr_fused = 1;
   select_pyr_plan(P, 0);  // the default; launch_pyramid picks per launch
 }
@@ -535,7 +641,8 @@ static bool qt_code_tables(const LevelGeom& g, std::vector<uint32_t>& t, int* bi
   return true;
 }
 
-static int build_plan(orbx_extractor* h, int W, int Hh, int B) {
+// The host part of a plan: geometry, tables and tilings. No device call.
+static int build_plan_host(orbx_extractor* h, int W, int Hh, int B) {
   Plan& pl = h->plan;
   const orbx_config& c = h->cfg;
   const int L = c.nlevels;
@@ -773,8 +880,18 @@ static int build_plan(orbx_extractor* h, int W, int Hh, int B) {
   pl.W = W;
   pl.H = Hh;
   pl.B = B;
-  // device buffers (the pyramid's level-0 planes stay unused: level 0 is the caller's frames)
+  pl.level_bytes = lvl_off;
+  return ORBX_OK;
+}
+
+static int build_plan(orbx_extractor* h, int W, int Hh, int B) {
   int rc;
+  if ((rc = build_plan_host(h, W, Hh, B))) return rc;
+  Plan& pl = h->plan;
+  const ExtractParams& P = pl.P;
+  const int L = P.L, slot = P.slots_per_frame;
+  const long long lvl_off = pl.level_bytes;
+  // device buffers (the pyramid's level-0 planes stay unused: level 0 is the caller's frames)
   if ((rc = pl.pyr.alloc((size_t)lvl_off))) return rc;
   if ((rc = pl.blur.alloc((size_t)lvl_off))) return rc;
   if ((rc = pl.rtab_d.alloc(std::max<size_t>(pl.rtab.size(), 1) * sizeof(int2)))) return rc;
@@ -1007,6 +1124,28 @@ int orbx_destroy(orbx_handle h) {
 }
 
 int orbx_frame_capacity(orbx_handle h) { return h ? h->plan.P.kp_per_frame : 0; }
+
+/* Internal, for the tests (not part of orbx_c.h, needs no device): plans `cfg`
+ * on the host and checks the band pyramid's column records of every kept plan
+ * (pyr_records_ok). *nplans: the kept plans (0: the per-level kernel runs);
+ * records[i]: plan i's records checked, -1 if a bound fails. */
+int orbx_pyr_plan_check(const orbx_config* cfg, long long* records, int cap, int* nplans) {
+  if (!cfg || !records || !nplans) return fail(ORBX_EINVAL, "null argument");
+  if (cfg->nlevels < 1 || cfg->nlevels > kMaxLevels || !(cfg->scale_factor > 1.0f) || cfg->width <= 0 ||
+      cfg->height <= 0 || cfg->max_batch < 1)
+    return fail(ORBX_EINVAL, "bad configuration");
+  orbx_extractor* h = new orbx_extractor();
+  h->cfg = *cfg;
+  compute_scales(h);
+  const int rc = build_plan_host(h, cfg->width, cfg->height, cfg->max_batch);
+  if (!rc) {
+    const ExtractParams& P = h->plan.P;
+    *nplans = P.pyr_fused ? P.pyr_nplans : 0;
+    for (int i = 0; i < *nplans && i < cap; ++i) records[i] = pyr_records_ok(P, h->plan.rtab, P.pyr_plan[i]);
+  }
+  delete h;
+  return rc;
+}
 
 int orbx_extract_batch(orbx_handle h, const uint8_t* d_frames, int batch, size_t frame_pitch, size_t row_stride,
                        orbx_kp* d_kps, uint8_t* d_desc, int* d_counts, void* stream) {

@@ -97,9 +97,11 @@ struct ExtractParams {
   // band pyramid (orbx_pyramid.hip): one workgroup per (frame, band of rows, column tile)
   int pyr_fused;               // 0 = one launch per level instead
   int pyr_nbands;              // bands per frame
-  int pyr_bands;               // int2 offset in the resize table: per (band, level) {comp_lo, comp_hi}, {own_lo, own_hi}
+  int pyr_bands;               // int2 offset in the resize table: per (band, level) {comp_lo, comp_hi}, {own_lo, own_hi};
+                               // level 0's second entry: {int2 offset of the band's staged row entries, their count}
   int pyr_nct;                 // column tiles per band
-  int pyr_ctiles;              // int2 offset: per (tile, level) {comp_lo, comp_hi}, {own_lo, own_hi}, {LDS pitch, LDS origin}
+  int pyr_ctiles;              // int2 offset: per (tile, level) {comp_lo, comp_hi}, {own_lo, own_hi}, {LDS pitch, LDS origin},
+                               // {int2 offset of the level's column records (orbx_host.hip plan_band_pyramid), 0}
   int pyr_lds_a, pyr_lds_b;    // LDS bytes of the even-level and odd-level row buffers
   int pyr_lds_y;               // LDS bytes of the band's staged row coefficients
   // alternative tilings, one picked per launch (launch_pyramid): the

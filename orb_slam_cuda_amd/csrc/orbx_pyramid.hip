@@ -144,10 +144,9 @@ __global__ __launch_bounds__(256) void pyr_resize_kernel(
 #define ORBX_PYR_THREADS 512
 #endif
 constexpr int kPyrBandThreads = ORBX_PYR_THREADS;
-// the 2x2 area mean as coefficients of the bilinear loop (band_row): a0 = a1 =
-// 2048, 4*b0 = 4*b1 = 2048
-constexpr uint32_t kPyrAreaA = 2048u | (2048u << 16);
-constexpr int kPyrAreaB4 = 2048 | (2048 << 16);
+// (the 2x2 area mean runs through the bilinear loop, band_row, with the
+// coefficients a0 = a1 = 2048 and 4*b0 = 4*b1 = 2048 in the host's column
+// records and row entries)
 // waves per SIMD the band kernel is compiled for (5: <= 96 VGPRs, two
 // 512-thread workgroups per CU; 6 would allow three at <= 53 KB of LDS)
 #ifndef ORBX_PYR_WPE
@@ -223,7 +222,7 @@ __device__ __forceinline__ uint32_t band_mad24(uint32_t a, uint32_t b, uint32_t 
 // a0 + a1 and b0 + b1 are at most 2049, so the sum is at most
 // 4 * (255 * 2049 * 2049 + 2^21) = 4 290 757 628 < 2^32 with every term >= 0,
 // and its top byte is at most 255: no clamp. The 2x2 area mean runs through the
-// same code with a0 = a1 = 2048 and 4b0 = 4b1 = 2048 (the kernel's constants):
+// same code with a0 = a1 = 2048 and 4b0 = 4b1 = 2048 (the host's tables):
 // ((p00 + p01 + p10 + p11) * 2^22 + 2^23) >> 24 = (sum + 2) >> 2.
 struct BandRowCtx {
   const uint8_t* src;   // the source level's LDS tile, row src_lo first
@@ -273,6 +272,14 @@ __device__ __forceinline__ void band_row(const BandRowCtx& c, int r, uint32_t lo
   }
 }
 
+// Diagnostics (tools/variant.sh; wrong pixels, timing only): the bound of what
+// building level 1 from global memory, without the level-0 tile in LDS, could
+// save. ORBX_PYR_NOSTAGE skips the level-0 staging
+// altogether; ORBX_PYR_STAGE_NOLDS issues its loads but does not write them to LDS.
+#if (defined(ORBX_PYR_NOSTAGE) || defined(ORBX_PYR_STAGE_NOLDS)) && !defined(ORBX_DIAG)
+#error "result-changing diagnostic switches need -DORBX_DIAG (tools/variant.sh)"
+#endif
+
 __global__ __launch_bounds__(kPyrBandThreads) __attribute__((amdgpu_waves_per_eu(ORBX_PYR_WPE))) void pyr_band_kernel(ExtractParams P, LevelPtrs lp,
                                                                    const int2* __restrict__ rtab, int* dbg) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -281,51 +288,23 @@ __global__ __launch_bounds__(kPyrBandThreads) __attribute__((amdgpu_waves_per_eu
   const int wg = xcd_remap(blockIdx.x, gridDim.x);
   const int f = wg / (nb * nct), tile = wg - f * (nb * nct), band = tile / nct, ct = tile - band * nct;
   const int2* bt = rtab + P.pyr_bands + (long long)band * L * 2;  // {comp}, {own} rows per level
-  const int2* xt = rtab + P.pyr_ctiles + (long long)ct * L * 3;   // {comp}, {own} columns, {LDS pitch, origin}
+  const int2* xt = rtab + P.pyr_ctiles + (long long)ct * L * 4;   // {comp}, {own} columns, {LDS pitch, origin}, {records}
   uint8_t* const bufA = smem;
   uint8_t* const bufB = smem + P.pyr_lds_a;
   // the band's row coefficients of every level, staged once: a global load
   // per output row would put one memory latency on every row iteration
   int2* const s_yt = (int2*)(smem + P.pyr_lds_a + P.pyr_lds_b);
-  // one staged row coefficient per thread (rows of levels 1..L-1 flattened;
-  // bands hold far fewer than kPyrBandThreads rows, larger ones loop), its
-  // load issued before the level-0 loads so that both are in flight together
-  // (no early exit and constant level indices: the band table and level
-  // fields are scalar loads issued together)
-  int yrow = 0, ytot = 0, yarea = 1, ytab = 0;
-#pragma unroll
-  for (int l = 1; l < kMaxLevels; ++l) {
-    const int2 cd = bt[2 * min(l, L - 1)];
-    const int n = l < L ? cd.y - cd.x + 1 : 0;
-    if (tid >= ytot && tid < ytot + n) {
-      yrow = cd.x + tid - ytot;
-      yarea = P.lv[l].area2x;
-      ytab = P.lv[l].ytab;
-    }
-    ytot += n;
-  }
-  // staged entry: {sy0 | sy1 << 16, 4*b0 | 4*b1 << 16} (band_row; 4 * 2048 fits 16 bits)
-  auto y_entry = [&](int area, int tab, int r) {
-    if (area) return make_int2((2 * r) | ((2 * r + 1) << 16), kPyrAreaB4);
-    const int2 e = rtab[tab + r];
-    return make_int2(e.x, e.y << 2);
-  };
+  // one staged row entry per thread, {sy0 | sy1 << 16, 4*b0 | 4*b1 << 16}
+  // (band_row; 4 * 2048 fits 16 bits): the band's rows of levels 1..L-1
+  // flattened, a list the host makes per band (plan_band_pyramid; the band
+  // table's level-0 own entry holds {its offset, its length}). Bands hold far
+  // fewer than kPyrBandThreads rows, larger ones loop. The load is issued
+  // before the level-0 loads so that both are in flight together.
+  const int2 yh = bt[1];
+  const int ytot = yh.y;
   int2 yval = make_int2(0, 0);
-  if (tid < ytot) yval = y_entry(yarea, ytab, yrow);
-  for (int i = tid + kPyrBandThreads; i < ytot; i += kPyrBandThreads) {  // very tall bands only
-    int rem = i;
-    for (int l = 1; l < L; ++l) {
-      const int2 cd = bt[2 * l];
-      const int n = cd.y - cd.x + 1;
-      if (rem < n) {
-        const LevelGeom& g = P.lv[l];
-        const int r = cd.x + rem;
-        s_yt[i] = y_entry(g.area2x, g.ytab, r);
-        break;
-      }
-      rem -= n;
-    }
-  }
+  if (tid < ytot) yval = rtab[yh.x + tid];
+  for (int i = tid + kPyrBandThreads; i < ytot; i += kPyrBandThreads) s_yt[i] = rtab[yh.x + i];  // very tall bands only
 
   // ---- stage level-0 rows [comp_lo, comp_hi] x the tile's columns, 4 loads in flight per thread
   {
@@ -340,7 +319,11 @@ __global__ __launch_bounds__(kPyrBandThreads) __attribute__((amdgpu_waves_per_eu
       const int nch = ((xe - org) >> 4) + 1, total = rows * nch;  // at most a CU's LDS / 16
       const float rnch = __builtin_amdgcn_rcpf((float)nch);
       // unpredicated (indices past the end repeat the last chunk)
+#ifdef ORBX_PYR_NOSTAGE
+      for (int i0 = tid; i0 < 0; i0 += 4 * kPyrBandThreads) {
+#else
       for (int i0 = tid; i0 < total; i0 += 4 * kPyrBandThreads) {
+#endif
         u32x4 v[4];
         int so[4], lo[4];
 #pragma unroll
@@ -353,10 +336,19 @@ __global__ __launch_bounds__(kPyrBandThreads) __attribute__((amdgpu_waves_per_eu
 #pragma unroll
         for (int q = 0; q < 4; ++q) v[q] = *(const u32x4*)(S + lo[q]);
         if (i0 == tid && tid < ytot) s_yt[tid] = yval;
+#ifdef ORBX_PYR_STAGE_NOLDS
+#pragma unroll
+        for (int q = 0; q < 4; ++q) asm volatile("" ::"v"(v[q]));  // the loads stay, their LDS writes go
+#else
 #pragma unroll
         for (int q = 0; q < 4; ++q) *(u32x4*)(bufA + so[q]) = v[q];
+#endif
       }
+#ifdef ORBX_PYR_NOSTAGE
+      if (tid < ytot) s_yt[tid] = yval;
+#else
       if (tid >= total && tid < ytot) s_yt[tid] = yval;
+#endif
     } else {
       if (tid < ytot) s_yt[tid] = yval;
       const int ncol = xe - org + 1;
@@ -365,15 +357,17 @@ __global__ __launch_bounds__(kPyrBandThreads) __attribute__((amdgpu_waves_per_eu
     }
   }
 
-  // column coefficients: level l+1's are fetched while level l is computed
-  int2 nxt[8];
+  // the thread's column record (BandCols and its store flags, made on the
+  // host: plan_band_pyramid): level l+1's is fetched while level l is computed
+  typedef unsigned int rec4_t __attribute__((ext_vector_type(4)));
+  rec4_t nxt[5];
+  uint32_t nxt_flags = 0;
   int nxt_gi = 0, nxt_ra = 0, nxt_rb = -1;  // the thread's column group and rows [ra, rb] at that level
   // a thread's 8 columns are 4 runs of 2 (pyr_col) with G = ceil(width/8)
   // over the tile's computed columns: neighbouring lanes read source bytes a
   // run's width x 1.2 apart
   auto fetch_cols = [&](int l) {
-    const LevelGeom& g = P.lv[l];
-    const int2 xc = xt[3 * l];
+    const int2 xc = xt[4 * l];
     const int G = (xc.y - xc.x + 1 + 7) >> 3;
     const float rG = __builtin_amdgcn_rcpf((float)G);
     const int chunk = band_div(tid, rG), gi = tid - chunk * G;
@@ -390,8 +384,10 @@ __global__ __launch_bounds__(kPyrBandThreads) __attribute__((amdgpu_waves_per_eu
     nxt_gi = gi;
     nxt_ra = cd.x + chunk * len + min(chunk, rem);
     nxt_rb = chunk < nchunks ? nxt_ra + len - (chunk < rem ? 0 : 1) : nxt_ra - 1;
+    const rec4_t* rec = (const rec4_t*)(rtab + xt[4 * l + 3].x) + __mul24(gi, 6);
 #pragma unroll
-    for (int q = 0; q < 8; ++q) nxt[q] = rtab[g.xtab2 + min(xc.x + pyr_col(gi, G, q), g.w - 1)];
+    for (int i = 0; i < 5; ++i) nxt[i] = rec[i];
+    nxt_flags = ((const uint32_t*)rec)[20];
   };
   fetch_cols(1);
   lds_sync();  // LDS only: the owned rows written to HBM are not read back here
@@ -405,19 +401,17 @@ __global__ __launch_bounds__(kPyrBandThreads) __attribute__((amdgpu_waves_per_eu
   // first row of a chunk or after a step of two source rows).
   int yoff = 0;
   for (int l = 1; l < L; ++l) {
-    const LevelGeom& g = P.lv[l];
     const int2 cs = bt[2 * (l - 1)], cd = bt[2 * l], own = bt[2 * l + 1];
-    const int2 xc = xt[3 * l], xo = xt[3 * l + 1], sp = xt[3 * (l - 1) + 2], dp = xt[3 * l + 2];
+    const int2 xc = xt[4 * l], sp = xt[4 * (l - 1) + 2], dp = xt[4 * l + 2];
     const int G = (xc.y - xc.x + 1 + 7) >> 3, gi = nxt_gi, ra = nxt_ra, rb = nxt_rb;
     BandCols bc;
 #pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      const int sx = nxt[q].x - sp.y;  // LDS-relative: the source level's row starts at column sp.y
-      if (!(q & 1)) bc.off[q >> 1] = sx & ~3;
-      const uint32_t o = (uint32_t)(sx - bc.off[q >> 1]);  // 0 .. 6
-      bc.sel[q] = 0x0c000c00u | o | ((o + 1) << 16);
-      bc.a01[q] = g.area2x ? kPyrAreaA : (uint32_t)nxt[q].y;
+    for (int q = 0; q < 4; ++q) {
+      bc.off[q] = (int)nxt[0][q];
+      bc.sel[q] = nxt[1][q], bc.sel[4 + q] = nxt[2][q];
+      bc.a01[q] = nxt[3][q], bc.a01[4 + q] = nxt[4][q];
     }
+    const uint32_t flags = nxt_flags;
     if (l + 1 < L) fetch_cols(l + 1);
     BandRowCtx c;
     c.src = (l & 1) ? bufA : bufB;
@@ -427,12 +421,11 @@ __global__ __launch_bounds__(kPyrBandThreads) __attribute__((amdgpu_waves_per_eu
     c.own_lo = (unsigned)own.x, c.own_n = (unsigned)(own.y - own.x + 1);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const int gx = xc.x + 2 * (gi + k * G);
       c.g[k] = (uint8_t*)lp.base[l] + f * lp.fstride[l] + xc.x + 2 * k * G;
-      c.st2[k] = gx >= xo.x && gx < xo.y;
-      c.st1[k] = gx == xo.y;
+      c.st2[k] = (flags >> k) & 1u;
+      c.st1[k] = (flags >> (4 + k)) & 1u;
     }
-    c.any1 = c.st1[0] | c.st1[1] | c.st1[2] | c.st1[3];
+    c.any1 = (flags & 0xF0u) != 0;
     // 32-bit offsets of the thread's first run in the LDS tile and in the
     // level's plane (level sides are at most 4096), advanced by a pitch per row
     uint32_t loff = (uint32_t)(__mul24(ra - cd.x, c.dpitch) + 2 * gi);
