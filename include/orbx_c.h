@@ -79,6 +79,17 @@
  *   orbv_transform         Frame::ComputeBoW  src/Frame.cc:394-401 ->
  *                          TemplatedVocabulary::transform(features, BowVector,
  *                          FeatureVector, levelsup)  TemplatedVocabulary.h:1127-1256
+ *   orbv_score             ORBVocabulary::score(v1, v2) (LoopClosing::DetectLoop
+ *                          src/LoopClosing.cc:160), the six DBoW2 scorings
+ *                          Thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-311
+ *   orbdb_add / orbdb_add_batch / orbdb_erase / orbdb_clear  KeyFrameDatabase::
+ *                          add / erase / clear  src/KeyFrameDatabase.cc:76-109
+ *   orbdb_query + orbdb_select_candidates  KeyFrameDatabase::DetectLoopCandidates
+ *                          (:112-233, LoopClosing::DetectLoop src/LoopClosing.cc:173)
+ *                          and DetectRelocalizationCandidates (:235-345,
+ *                          Tracking::Relocalization src/Tracking.cc:1436)
+ *   orbdb_query_batch      their counting and scoring, batched on device
+ *   orbdb_score_slots      the score loop over covisibles src/LoopClosing.cc:147-165
  *
  * Error behaviour: every call returns ORBX_OK or a negative code; the
  * message of the last failure on the calling thread is orbx_last_error().
@@ -834,6 +845,141 @@ int orbv_transform_batch(orbv_handle v, const uint8_t* d_desc, size_t desc_pitch
                          uint32_t* d_fv_nodes, int* d_fv_off, int* d_fv_idx,
                          int* d_fv_n, uint32_t* d_word_ids, uint32_t* d_node_ids,
                          double* d_weights, void* stream);
+
+/* TemplatedVocabulary::score(v1, v2) = GeneralScoring::score of the
+ * vocabulary's scoring type (Thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-311)
+ * for two BowVectors given as ascending words with their values. `scoring`
+ * as for orbv_create; all six are covered. The doubles are the reference
+ * loops' bit for bit: terms are added in the order of the walk, L1 ends with
+ * score = -score/2.0, KL uses LOG_EPS = log(DBL_EPSILON) and its asymmetric
+ * walk (:175-221: every word of v1 counts, v2's only where shared). Host
+ * only: no device, no handle. The message of a failure is orbdb_last_error(). */
+int orbv_score(int scoring, const uint32_t* w1, const double* v1, int n1,
+               const uint32_t* w2, const double* v2, int n2, double* out);
+
+/* ------------------------------------------- keyframe database (BoW scores)
+ * KeyFrameDatabase (src/KeyFrameDatabase.cc) with the keyframes' BowVectors
+ * resident on the device: one row of up to word_pitch (word, value) pairs per
+ * slot, words and values in separate arrays. A keyframe is named by its slot.
+ * The reference's inverted file is not kept: a query intersects its sorted
+ * words with every live row. scoring must be L1 (0), the scoring of
+ * ORBvoc.txt; any other returns ORBX_EINVAL with a message naming it.
+ *
+ * Ordering: mutations and queries of one handle are ordered by the library
+ * across streams (each waits for the previous user of the storage, as the
+ * matcher's workspaces do). A handle is not reentrant. The message of the
+ * last failure on the calling thread is orbdb_last_error(). */
+typedef struct orbdb_database* orbdb_handle;
+
+const char* orbdb_last_error(void);
+
+/* max_keyframes slots of word_pitch pairs (1 .. 8192, the cap of
+ * orbv_transform) on `device`: 12 bytes per pair of device memory. */
+int orbdb_create(int device, int max_keyframes, int word_pitch, int scoring, orbdb_handle* out);
+int orbdb_destroy(orbdb_handle db);
+/* KeyFrameDatabase::clear (:105-109): every slot dead. The add sequence
+ * counter goes on counting. Synchronous. */
+int orbdb_clear(orbdb_handle db);
+/* *live = entries in the database, *slots_high_water = one past the highest
+ * slot ever used since the last clear (either may be NULL). Host only. */
+int orbdb_size(orbdb_handle db, int* live, int* slots_high_water);
+
+/* KeyFrameDatabase::add (:76-82) of a BowVector on the host (ascending words,
+ * checked; synchronous). The entry takes the lowest free slot (*slot) and the
+ * next value of the handle's 32-bit add sequence counter, which never
+ * repeats within a handle and orders the entries as the reference's
+ * per-word lists do (insertion order). n = 0 is a legal entry that shares no
+ * word with anything. ORBX_ECAPACITY: max_keyframes entries are live already,
+ * or n > word_pitch. The slot's relocalisation score (below) is set to 0. */
+int orbdb_add(orbdb_handle db, const uint32_t* words, const double* values, int n, int* slot);
+
+/* The same for `frames` BowVectors where orbv_transform_batch left them on
+ * the device (its layout at pitch = its cap): frame f's d_bow_n[f] pairs at
+ * f*pitch. slots (host, `frames` ints) receives their slots, assigned in
+ * frame order. d_bow_n is needed on the host to validate (a count above
+ * word_pitch is ORBX_ECAPACITY, and then nothing is added): the call copies
+ * it back and waits for `stream` once before it enqueues the row copies,
+ * which are asynchronous on `stream`. The rows are trusted to ascend. */
+int orbdb_add_batch(orbdb_handle db, const uint32_t* d_bow_words, const double* d_bow_values,
+                    const int* d_bow_n, int pitch, int frames, int* slots, void* stream);
+
+/* KeyFrameDatabase::erase (:84-103). ORBX_EINVAL for a slot that is not
+ * live. Synchronous. */
+int orbdb_erase(orbdb_handle db, int slot);
+
+/* What the two Detect functions compute per keyframe. 16 bytes. */
+typedef struct orbdb_hit {
+  int32_t common;      /* words shared with the query: mnLoopWords / mnRelocWords */
+  uint32_t first_word; /* the smallest shared word id (0 when common == 0)       */
+  double score;        /* L1 score where common > minCommon, else -1.0           */
+} orbdb_hit;
+
+/* `queries` BowVectors (device, the layout of orbv_transform_batch at
+ * `pitch` <= 8192; a count above pitch is read as pitch) against every slot,
+ * asynchronous on `stream`. d_hits: queries x max_keyframes records, query
+ * q's slot s at q*max_keyframes + s; d_max_common: queries ints.
+ * common = 0 for a dead slot, an empty entry and a slot in the query's
+ * exclude list (d_exclude + q*exclude_pitch, d_n_exclude[q] slots: the
+ * connected keyframes of DetectLoopCandidates :114,132; d_exclude NULL = none,
+ * as for relocalisation). d_max_common[q] = the maximum of common over the
+ * query's slots (maxCommonWords :149-154); minCommon = (int)(max * 0.8f) in
+ * float (:156, :271). score is written where common > minCommon (:165, :282)
+ * and equals orbv_score(0, query, keyframe) bit for bit: the terms of the
+ * shared words are added one at a time in ascending word order from +0.0.
+ * Elsewhere score is -1.0. */
+int orbdb_query_batch(orbdb_handle db, const uint32_t* d_bow_words, const double* d_bow_values,
+                      const int* d_bow_n, int pitch, int queries, const int* d_exclude,
+                      const int* d_n_exclude, int exclude_pitch, orbdb_hit* d_hits,
+                      int* d_max_common, void* stream);
+
+/* mpORBVocabulary->score(CurrentBowVec, pKF->mBowVec) over entries of the
+ * database (LoopClosing::DetectLoop's covisibles, src/LoopClosing.cc:147-165):
+ * out[k] = orbv_score(0, query, entry slots[k]) bit for bit, by the device
+ * code that scores the queries above. Synchronous. ORBX_EINVAL for a slot
+ * that is not live. */
+int orbdb_score_slots(orbdb_handle db, const uint32_t* words, const double* values, int n,
+                      const int* slots, int nslots, double* out);
+
+#define ORBDB_LOOP 0  /* DetectLoopCandidates            :112-233 */
+#define ORBDB_RELOC 1 /* DetectRelocalizationCandidates  :235-345 */
+
+/* The first half of a Detect function, one device round trip (synchronous):
+ * lScoreAndMatch as (slot, si = (float)score) pairs in the reference's list
+ * order, i.e. first encounter when the query's words are walked upwards with
+ * each word's inverted list in insertion order = ascending (first_word, add
+ * sequence). ORBDB_LOOP lists the entries with si >= min_score (:172) and
+ * takes `exclude` (n_exclude slots) = pKF->GetConnectedKeyFrames();
+ * ORBDB_RELOC lists every scored entry and ignores min_score. *ncand = their
+ * number (ORBX_ECAPACITY when above cap; the first cap are written),
+ * *min_common = minCommonWords (may be NULL). The ordering and everything
+ * after the kernels run on the host over the copied-back hits. The handle
+ * remembers, per mode, each slot's common, minCommon and score for
+ * orbdb_select_candidates. Each call is a fresh query id: what the reference
+ * does when one mnId queries twice (stale mnLoopQuery / mnRelocQuery marks)
+ * is not reproduced. */
+int orbdb_query(orbdb_handle db, int mode, const uint32_t* words, const double* values, int n,
+                const int* exclude, int n_exclude, float min_score, int* cand_slots,
+                float* cand_scores, int cap, int* ncand, int* min_common);
+
+/* The second half (:180-232, :294-344) on the last orbdb_query of `mode`,
+ * operation by operation: accScore a float sum over the candidate and its
+ * counting neighbours, best score by strict >, bestAccScore starting at
+ * min_score (loop) or 0 (relocalisation), retained where accScore >
+ * 0.75f * bestAccScore, duplicates dropped in first-seen order. neigh: ncand
+ * x 10 slots, candidate i's GetBestCovisibilityKeyFrames(10), -1 = none (the
+ * library has no covisibility graph). A neighbour counts in loop mode if it
+ * was listed by the query and its common > minCommon, in relocalisation mode
+ * if it shares a word with the query; its mLoopScore / mRelocScore is added.
+ * In relocalisation mode that score is stale when this query did not score
+ * the neighbour: the handle keeps a per-slot relocalisation score across
+ * queries, rewritten only when the slot is scored and set to 0.0f by add.
+ * (Parity-unpinned: the reference reads a float that src/KeyFrame.cc:44
+ * leaves uninitialised until the first scoring; 0 is this library's
+ * definition.) out_slots: ncand ints; *nout = the candidates kept. Host
+ * only. */
+int orbdb_select_candidates(orbdb_handle db, int mode, const int* cand_slots,
+                            const float* cand_scores, int ncand, const int* neigh,
+                            float min_score, int* out_slots, int* nout);
 
 /* ------------------------------------------------ SearchForTriangulation
  * Per pair: F12 (row-major 3x3, LocalMapping::ComputeF12) and the epipole

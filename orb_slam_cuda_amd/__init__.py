@@ -11,8 +11,9 @@ from .matcher import (ComputeImageBounds, ComputeStereoFromRGBD, ComputeStereoMa
                       ComputeStereoMatchesLast, ExtractRGBD, ExtractStereo, Frame, KeyFrame, MapPoints, ORBmatcher,
                       UndistortKeyPoints)
 from .vocabulary import ComputeBoW, ORBVocabulary  # noqa: F401
+from .database import KeyFrameDatabase  # noqa: F401
 
-__all__ = ["ORBextractor", "ORBmatcher", "ORBVocabulary", "Frame", "KeyFrame", "ComputeBoW",
+__all__ = ["ORBextractor", "ORBmatcher", "ORBVocabulary", "Frame", "KeyFrame", "ComputeBoW", "KeyFrameDatabase",
            "ComputeStereoMatches", "ComputeStereoMatchesLast", "ExtractStereo", "MapPoints", "KP_DTYPE", "OrbxError",
            "device_count", "header_functions", "lib", "UndistortKeyPoints", "ComputeImageBounds",
            "ComputeStereoFromRGBD", "ExtractRGBD"]

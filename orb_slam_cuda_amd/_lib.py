@@ -254,6 +254,24 @@ def lib() -> C.CDLL:
         L.orbv_transform.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 10
         L.orbv_transform_batch.argtypes = ([C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int,
                                             C.c_int] + [C.c_void_p] * 11)
+        L.orbv_score.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                 C.POINTER(C.c_double)]
+        L.orbdb_last_error.restype = C.c_char_p
+        L.orbdb_create.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_void_p)]
+        L.orbdb_destroy.argtypes = [C.c_void_p]
+        L.orbdb_clear.argtypes = [C.c_void_p]
+        L.orbdb_size.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.orbdb_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        L.orbdb_add_batch.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.orbdb_erase.argtypes = [C.c_void_p, C.c_int]
+        L.orbdb_query_batch.argtypes = ([C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+                                        + [C.c_void_p] * 3)
+        L.orbdb_score_slots.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        L.orbdb_query.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                  C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int),
+                                  C.POINTER(C.c_int)]
+        L.orbdb_select_candidates.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                              C.c_float, C.c_void_p, C.POINTER(C.c_int)]
         L.orbx_device_count.argtypes = [C.POINTER(C.c_int)]
         L.orbx_set_device.argtypes = [C.c_int]
         L.orbx_malloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
@@ -308,10 +326,16 @@ MAP_POINT_PROJ_DTYPE = np.dtype([("proj_x", "<f4"), ("proj_y", "<f4"), ("proj_xr
                                  ("pad", "u1", (2,))])
 
 
-def check(rc: int, matcher: bool = False, vocabulary: bool = False) -> None:
+# orbdb_hit (include/orbx_c.h), 16 bytes
+DB_HIT_DTYPE = np.dtype([("common", "<i4"), ("first_word", "<u4"), ("score", "<f8")])
+assert DB_HIT_DTYPE.itemsize == 16
+ORBDB_LOOP, ORBDB_RELOC = 0, 1
+
+
+def check(rc: int, matcher: bool = False, vocabulary: bool = False, database: bool = False) -> None:
     if rc != ORBX_OK:
         L = lib()
-        msg = (L.orbv_last_error() if vocabulary else
+        msg = (L.orbdb_last_error() if database else L.orbv_last_error() if vocabulary else
                L.orbm_last_error() if matcher else L.orbx_last_error()) or b""
         raise OrbxError(rc, msg.decode(errors="replace"))
 
@@ -320,7 +344,7 @@ def header_functions(path: str = HEADER) -> list[str]:
     """Names of every function declared in include/orbx_c.h."""
     src = open(path).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b((?:orbx|orbm|orbv)_[a-z0-9_]+)\s*\(", src)))
+    return sorted(set(re.findall(r"\b((?:orbx|orbm|orbv|orbdb)_[a-z0-9_]+)\s*\(", src)))
 
 
 def ptr(a) -> C.c_void_p:

@@ -373,6 +373,8 @@ class KeyFrame:
     mbf: float = 0.0
     mvLevelSigma2: np.ndarray | None = None
     mvInvLevelSigma2: np.ndarray | None = None
+    mBowVec: dict = field(default_factory=dict)   # {WordId: value} (ComputeBoW); read by KeyFrameDatabase
+    mnId: int = 0
 
     def GetCameraCenter(self) -> np.ndarray:
         """Ow = -Rcw^T tcw (KeyFrame::SetPose, src/KeyFrame.cc:77-92)."""

@@ -105,6 +105,33 @@ class ORBVocabulary:
               for k, nd in enumerate(r["fv_nodes"])}
         return bow, fv
 
+    # ---------------------------------------------------------- score
+    def score(self, a: dict, b: dict) -> float:
+        """TemplatedVocabulary::score(v1, v2) of two BowVectors as transform returns
+        them, with the vocabulary's scoring type (ScoringObject.cpp:23-311). Host only."""
+        return bow_score(self._info()[2], a, b)
+
+
+def bow_arrays(bow) -> tuple:
+    """A BowVector ({WordId: value} or a (words, values) pair) as ascending uint32 words
+    and their float64 values (std::map order)."""
+    if isinstance(bow, dict):
+        w = np.fromiter(bow.keys(), np.uint32, len(bow))
+        v = np.fromiter(bow.values(), np.float64, len(bow))
+        o = np.argsort(w, kind="stable")
+        return np.ascontiguousarray(w[o]), np.ascontiguousarray(v[o])
+    w, v = bow
+    return np.ascontiguousarray(w, np.uint32), np.ascontiguousarray(v, np.float64)
+
+
+def bow_score(scoring: int, a, b) -> float:
+    """orbv_score: the DBoW2 scoring `scoring` (L1 0 .. DOT_PRODUCT 5) of two BowVectors."""
+    (w1, v1), (w2, v2) = bow_arrays(a), bow_arrays(b)
+    out = C.c_double(0)
+    check(lib().orbv_score(int(scoring), ptr(w1), ptr(v1), len(w1), ptr(w2), ptr(v2), len(w2), C.byref(out)),
+          database=True)
+    return out.value
+
 
 def ComputeBoW(F, voc: ORBVocabulary, levelsup: int = 4) -> None:
     """Frame::ComputeBoW (src/Frame.cc:394-401): mBowVec / mFeatVec of the frame's

@@ -39,6 +39,20 @@ void ORBVocabulary::transform(const std::vector<cv::Mat>& features, DBoW2::BowVe
     fv.emplace_hint(fv.end(), nodes[k], std::vector<unsigned int>(idx.begin() + off[k], idx.begin() + off[k + 1]));
 }
 
+double ORBVocabulary::score(const DBoW2::BowVector& a, const DBoW2::BowVector& b) const {
+  int k, L, scoring = 0, w, nn, nw;
+  if (!h_ || orbv_info(h_, &k, &L, &scoring, &w, &nn, &nw) != ORBX_OK)
+    throw std::runtime_error("ORBVocabulary: empty vocabulary");
+  std::vector<uint32_t> wa, wb;
+  std::vector<double> va, vb;
+  for (const auto& e : a) wa.push_back(e.first), va.push_back(e.second);  // std::map: ascending words
+  for (const auto& e : b) wb.push_back(e.first), vb.push_back(e.second);
+  double s = 0;
+  if (orbv_score(scoring, wa.data(), va.data(), (int)wa.size(), wb.data(), vb.data(), (int)wb.size(), &s) != ORBX_OK)
+    throw std::runtime_error(std::string("liborbx: ") + orbdb_last_error());
+  return s;
+}
+
 unsigned int ORBVocabulary::size() const {
   int k, L, s, w, nn, nw = 0;
   if (!h_ || orbv_info(h_, &k, &L, &s, &w, &nn, &nw) != ORBX_OK) return 0;
