@@ -12,6 +12,6 @@ for i in 1 2; do
     OUT=$O/${v}_$i
     timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o run -- python3 bench.py --allow-diag --serial --steps 20 --warmup 3 --cpu-sample 0 --no-latency --no-host-stream > $OUT.log 2>&1 || { echo "$v $i failed"; tail -5 $OUT.log; exit 1; }
     echo "== $v $i"
-    python3 tools/stats_brief.py $OUT/run_kernel_stats.csv | grep -E "pyr_band|blur_kernel|fast_cells|orient_brief|quadtree"
+    python3 tools/stats_brief.py $OUT/run_kernel_stats.csv | grep -E "pyr_band|blur_kernel|fast_cells|orient_brief|quadtree|hamming_top2"
   done
 done | tee $O/summary.txt
