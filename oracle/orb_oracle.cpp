@@ -1290,8 +1290,10 @@ int orc_compute_stereo_matches(const orc_kp* kpL, const uint8_t* descL, int nL, 
     const int levelL = kpL_.octave;
     const float vL = kpL_.y;
     const float uL = kpL_.x;
-    const size_t row = (size_t)vL;  // vRowIndices[vL]: float -> size_t
-    if (row >= (size_t)nRows) continue;
+    // vRowIndices[vL]: float -> size_t in the reference, undefined for a
+    // negative vL; a keypoint above the image (or with a NaN row) gets no match
+    if (!(vL >= 0.0f && vL < (float)nRows)) continue;
+    const size_t row = (size_t)vL;
     const std::vector<size_t>& vCandidates = vRowIndices[row];
     if (vCandidates.empty()) continue;
     const float minU = uL - maxD;

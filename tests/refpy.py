@@ -354,9 +354,19 @@ def _c_round(v) -> float:
     return math.copysign(math.floor(abs(v) + 0.5), v)
 
 
-def compute_stereo_matches(kpL, dL, kpR, dR, pyrL, pyrR, scale, inv_scale, mb, mbf):
+def compute_stereo_matches(kpL, dL, kpR, dR, pyrL, pyrR, scale, inv_scale, mb, mbf, trace=None):
     """Frame::ComputeStereoMatches (src/Frame.cc:465-639). pyrL/pyrR: per-level 2-D u8.
-    Windows reaching off the level (an OpenCV range assertion there) give no match."""
+    Windows reaching off the level (an OpenCV range assertion there) give no match.
+
+    trace: a list that receives one dict per left keypoint: `stage`, where it
+    ended ("row": its row is off the image, holds no candidate, or uL < 0;
+    "hamming": best distance >= 75; "window": the SAD windows leave the level;
+    "edge_shift": best shift +-5; "delta": |deltaR| > 1; "disparity": outside
+    [0, mbf/mb); "median": dropped by the median rule; "kept"), and whatever was
+    computed before that: `best` (Hamming distance, 100 = none) and `iR`, `ul`,
+    `vl`, `ur0`, `sads` (11 ints), `bestinc`, `sad`, `deltaR`, `disparity` (before
+    the clamp to 0.01). The median rule's input is the `sad` of every record
+    whose stage is "kept" or "median"."""
     nL = len(kpL)
     uR_out = np.full(nL, -1.0, np.float32)
     dep_out = np.full(nL, -1.0, np.float32)
@@ -371,7 +381,11 @@ def compute_stereo_matches(kpL, dL, kpR, dR, pyrL, pyrR, scale, inv_scale, mb, m
     mb, mbf = f32(mb), f32(mbf)
     maxD = f32(mbf / mb)
     acc = []
+    recs = [dict(stage="row") for _ in range(nL)]
+    if trace is not None:
+        trace.extend(recs)
     for iL in range(nL):
+        rec = recs[iL]
         lev = int(kpL["octave"][iL])
         uL, vL = f32(kpL["x"][iL]), f32(kpL["y"][iL])
         if not (0 <= vL < nrows):
@@ -390,6 +404,7 @@ def compute_stereo_matches(kpL, dL, kpR, dR, pyrL, pyrR, scale, inv_scale, mb, m
                 d = hamming(dL[iL], dR[iR])
                 if d < best:
                     best, bi = d, iR
+        rec.update(stage="hamming", best=best, iR=bi)
         if best >= 75:
             continue
         sf = f32(inv_scale[lev])
@@ -399,6 +414,7 @@ def compute_stereo_matches(kpL, dL, kpR, dR, pyrL, pyrR, scale, inv_scale, mb, m
         A, B = pyrL[lev].astype(np.int64), pyrR[lev].astype(np.int64)
         h, w = A.shape
         ul, vl, ur = int(su), int(sv), int(sr)
+        rec.update(stage="window", ul=ul, vl=vl, ur0=ur)
         if ur < 10 or ul < 5 or ul + 5 >= w or vl < 5 or vl + 5 >= h:
             continue
         if sr < 0 or sr + 11 >= w:  # iniu / endu
@@ -410,15 +426,18 @@ def compute_stereo_matches(kpL, dL, kpR, dR, pyrL, pyrR, scale, inv_scale, mb, m
             dists.append(int(np.abs(IL - IR).sum()))
         binc = int(np.argmin(dists)) - 5  # first minimum
         bdist = min(dists)
+        rec.update(stage="edge_shift", sads=dists, bestinc=binc, sad=bdist)
         if binc in (-5, 5):
             continue
         d1, d2, d3 = (f32(dists[binc + 5 + k]) for k in (-1, 0, 1))
         with np.errstate(divide="ignore", invalid="ignore"):
             delta = f32(f32(d1 - d3) / f32(f32(2) * f32(f32(d1 + d3) - f32(f32(2) * d2))))
+        rec.update(stage="delta", deltaR=delta)
         if delta < -1 or delta > 1:
             continue
         buR = f32(f32(scale[lev]) * f32(f32(f32(sr) + f32(binc)) + delta))
         disp = f32(uL - buR)
+        rec.update(stage="disparity", disparity=disp)
         if disp >= 0 and disp < maxD:
             if disp <= 0:
                 disp = f32(0.01)
@@ -426,6 +445,7 @@ def compute_stereo_matches(kpL, dL, kpR, dR, pyrL, pyrR, scale, inv_scale, mb, m
             dep_out[iL] = f32(mbf / disp)
             uR_out[iL] = buR
             acc.append((bdist, iL))
+            rec["stage"] = "kept"
     if not acc:
         return uR_out, dep_out, 0
     acc.sort()
@@ -435,6 +455,7 @@ def compute_stereo_matches(kpL, dL, kpR, dR, pyrL, pyrR, scale, inv_scale, mb, m
         if f32(d) < th:
             break
         uR_out[i] = dep_out[i] = -1
+        recs[i]["stage"] = "median"
         kept -= 1
     return uR_out, dep_out, kept
 
