@@ -293,7 +293,9 @@ int orbm_destroy(orbm_handle m);
  * orbm_search_by_bow_batch saw a count above kp_pitch or a FeatureVector
  * index outside [0, n), which was skipped; bit 64:
  * orbm_search_local_points_batch found more than 8192 map points in view in
- * a frame, the points in view after the first 8192 were not searched).
+ * a frame, the points in view after the first 8192 were not searched; bit
+ * 128: orbm_refresh_map_points_batch / orbm_refresh_map_points skipped a
+ * point whose list names a keyframe, descriptor row or octave out of range).
  * SearchForInitialization keeps no
  * candidate lists (8 smallest keys per query) and never sets it. Waits for
  * the matcher's own launches that may set it (on whatever streams they ran),
@@ -634,6 +636,98 @@ int orbm_search_local_points_batch(
     const orbm_map_point_world* d_mps, const uint8_t* d_mpdesc, const int* d_nmp, int mp_pitch,
     int frames, float viewing_cos_limit, float th, float nnratio, int* d_out, int* d_nmatches,
     orbm_map_point_proj* d_proj, int* d_n_in_view, void* stream);
+
+/* ------ MapPoint::ComputeDistinctiveDescriptors, MapPoint::UpdateNormalAndDepth
+ * The two functions local mapping, Fuse / MapPoint::Replace, the monocular
+ * initialisation and loop closing call after a point's observations change
+ * (mostly together). They produce the fields the searches above read:
+ * orbm_map_point_world.normal / min_distance / max_distance and the point's
+ * 32-byte descriptor.
+ *
+ * orbm_observation: one entry of mObservations, kf = index into the
+ * keyframe table of the call, desc_row = row of pKF->mDescriptors.row(idx) in
+ * the descriptor arena. orbm_keyframe_ref: GetCameraCenter() and isBad() of a
+ * keyframe. orbm_point_refkf: mpRefKF as a keyframe index and
+ * mpRefKF->mvKeysUn[mObservations[mpRefKF]].octave. */
+typedef struct orbm_observation {
+  uint32_t kf, desc_row;
+} orbm_observation; /* 8 B */
+typedef struct orbm_keyframe_ref {
+  float Ow[3];
+  uint32_t bad;
+} orbm_keyframe_ref; /* 16 B */
+typedef struct orbm_point_refkf {
+  uint32_t kf;
+  int32_t octave;
+} orbm_point_refkf; /* 8 B */
+
+/* MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:277-306) on n
+ * gathered descriptors (32-byte rows, in std::map order, bad keyframes
+ * already left out): *best = the first row with the least median distance
+ * to all n rows (itself included; the median is element (n-1)/2 of the sorted
+ * row, a value in 0..256), *median (may be NULL) that median. n = 0: *best =
+ * *median = -1 (the reference returns with the descriptor untouched,
+ * :261-262, :274-275). Host only: runs without a device. */
+int orbm_distinctive_descriptor(const uint8_t* desc, int n, int* best, int* median);
+
+/* MapPoint::UpdateNormalAndDepth (src/MapPoint.cc:353-375) for one point:
+ * pos = mWorldPos, Ow_list = n camera centres (3 floats each) in std::map
+ * order (no isBad() test here: every observation counts), Ow_ref =
+ * mpRefKF->GetCameraCenter(), ref_scale = mvScaleFactors[level of the point's
+ * keypoint in mpRefKF], last_scale = mvScaleFactors[nLevels-1]. Writes
+ * mNormalVector, mfMinDistance, mfMaxDistance with the reference's float /
+ * double arithmetic operation by operation. n = 0 writes nothing
+ * (:350-351). Host only. */
+int orbm_update_normal_and_depth(const float* pos, const float* Ow_list, int n, const float* Ow_ref,
+                                 float ref_scale, float last_scale, float* normal_out,
+                                 float* min_distance, float* max_distance);
+
+/* Both, for `points` map points in place on the device, asynchronous on
+ * `stream`; nothing is read back. Point p of the call owns the observations
+ * d_obs[d_obs_off[p] .. d_obs_off[p+1]) (d_obs_off: points + 1 ascending
+ * entries; the list order is the caller's std::map order) and refreshes record
+ * q = d_point_ids ? d_point_ids[p] : p; an id repeated within one call is the
+ * caller's error. d_kfs: n_kfs keyframes; d_desc: one arena of desc_rows
+ * 32-byte rows, 16-byte aligned (an orbx_extract_batch output at its
+ * frame_capacity pitch: desc_row = frame*cap + idx); d_ref[p]: the point's
+ * reference keyframe and octave; scale: mvScaleFactors, nlevels <= 16 floats
+ * on the host.
+ * Written: d_mps[q].normal, .min_distance, .max_distance and no other byte of
+ * the record (pos is read); d_mpdesc[32*q .. 32*q+31] (16-byte aligned) =
+ * the winning row; d_best[p] = the winner's position among the point's kept
+ * observations (those whose keyframe is not bad) and d_median[p] its median,
+ * when these pointers are given. A point whose keyframes are all bad keeps
+ * its descriptor and gets d_best[p] = d_median[p] = -1, its normal and depth
+ * are still refreshed (:355 has no isBad() test). A point without observations
+ * gets d_best[p] = d_median[p] = -1 and nothing else.
+ * d_mps and d_ref NULL: descriptors only. d_mpdesc NULL: normal and depth
+ * only (d_best / d_median are still filled when given). d_point_ids NULL:
+ * q = p.
+ * A point with an observation whose kf >= n_kfs or desc_row >= desc_rows, or
+ * (with d_mps) whose d_ref[p].kf >= n_kfs or octave is outside [0, nlevels),
+ * is skipped as a whole: its record and descriptor stay untouched, d_best[p] =
+ * d_median[p] = -1, and status bit 128 is set (orbm_get_status). Any number
+ * of observations per point is accepted.
+ * The call's work lists live in the handle's workspace and are ordered like
+ * the other batched calls' (orbm_get_status). */
+int orbm_refresh_map_points_batch(
+    orbm_handle m, const orbm_observation* d_obs, const uint32_t* d_obs_off,
+    const uint32_t* d_point_ids, int points, const orbm_keyframe_ref* d_kfs, int n_kfs,
+    const uint8_t* d_desc, uint32_t desc_rows, const orbm_point_refkf* d_ref, const float* scale,
+    int nlevels, orbm_map_point_world* d_mps, uint8_t* d_mpdesc, int* d_best, int* d_median,
+    void* stream);
+
+/* The same on host arrays, synchronous, in one round trip: the arrays as
+ * above; mps / mpdesc are tables of n_mps records / descriptors (every id <
+ * n_mps, checked; n_mps >= points without ids) that are uploaded, refreshed
+ * and copied back whole. A skipped point (see above) is reported through
+ * status bit 128 here too; the call itself returns ORBX_OK. */
+int orbm_refresh_map_points(orbm_handle m, const orbm_observation* obs, const uint32_t* obs_off,
+                            const uint32_t* point_ids, int points, const orbm_keyframe_ref* kfs,
+                            int n_kfs, const uint8_t* desc, uint32_t desc_rows,
+                            const orbm_point_refkf* ref, const float* scale, int nlevels,
+                            orbm_map_point_world* mps, uint8_t* mpdesc, int n_mps, int* best,
+                            int* median);
 
 /* DBoW2::FeatureVector as CSR: nodes[k] ascending NodeIds; the feature
  * indices of node k are idx[off[k] .. off[k+1]). Each feature index appears

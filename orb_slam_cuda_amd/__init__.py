@@ -7,13 +7,13 @@ host-side mirror of the reference classes in Python.
 """
 from ._lib import KP_DTYPE, OrbxError, device_count, header_functions, lib  # noqa: F401
 from .extractor import ORBextractor  # noqa: F401
-from .matcher import (ComputeImageBounds, ComputeStereoFromRGBD, ComputeStereoMatches,  # noqa: F401
-                      ComputeStereoMatchesLast, ExtractRGBD, ExtractStereo, Frame, KeyFrame, MapPoints, ORBmatcher,
-                      UndistortKeyPoints)
+from .matcher import (ComputeDistinctiveDescriptors, ComputeImageBounds, ComputeStereoFromRGBD,  # noqa: F401
+                      ComputeStereoMatches, ComputeStereoMatchesLast, ExtractRGBD, ExtractStereo, Frame, KeyFrame,
+                      MapPoints, ORBmatcher, UndistortKeyPoints, UpdateNormalAndDepth)
 from .vocabulary import ComputeBoW, ORBVocabulary  # noqa: F401
 from .database import KeyFrameDatabase  # noqa: F401
 
 __all__ = ["ORBextractor", "ORBmatcher", "ORBVocabulary", "Frame", "KeyFrame", "ComputeBoW", "KeyFrameDatabase",
            "ComputeStereoMatches", "ComputeStereoMatchesLast", "ExtractStereo", "MapPoints", "KP_DTYPE", "OrbxError",
            "device_count", "header_functions", "lib", "UndistortKeyPoints", "ComputeImageBounds",
-           "ComputeStereoFromRGBD", "ExtractRGBD"]
+           "ComputeStereoFromRGBD", "ExtractRGBD", "ComputeDistinctiveDescriptors", "UpdateNormalAndDepth"]

@@ -227,6 +227,15 @@ def lib() -> C.CDLL:
         L.orbm_search_local_points_batch.argtypes = (
             [C.c_void_p] * 4 + [C.c_int, C.c_void_p, GridBounds, C.c_void_p, C.c_int, C.c_float] + [C.c_void_p] * 5
             + [C.c_int, C.c_int, C.c_float, C.c_float, C.c_float] + [C.c_void_p] * 5)
+        L.orbm_distinctive_descriptor.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.orbm_update_normal_and_depth.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_float,
+                                                   C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        L.orbm_refresh_map_points_batch.argtypes = ([C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                                                         C.c_uint32, C.c_void_p, C.c_void_p, C.c_int]
+                                                    + [C.c_void_p] * 5)
+        L.orbm_refresh_map_points.argtypes = ([C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_uint32,
+                                                                   C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                                                   C.c_void_p, C.c_int, C.c_void_p, C.c_void_p])
         L.orbm_prepare_sim3_match.argtypes = [C.POINTER(OrbmCamera), C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
                                               C.c_void_p, C.POINTER(OrbmPose)]
         L.orbm_fuse.argtypes = (PS + [C.c_void_p, GridBounds, C.c_void_p, C.c_void_p, C.c_int, C.c_float,
@@ -319,6 +328,13 @@ MAP_POINT_WORLD_DTYPE = np.dtype([("pos", "<f4", (3,)), ("normal", "<f4", (3,)),
 assert MAP_POINT_WORLD_DTYPE.itemsize == 48
 ORBM_PROJ_LAST_FRAME, ORBM_PROJ_KEYFRAME, ORBM_PROJ_SIM3 = 1, 2, 3
 ORBM_PROJ_FUSE, ORBM_PROJ_FUSE_SIM3, ORBM_PROJ_SIM3_MATCH = 4, 5, 6
+
+# orbm_observation, orbm_keyframe_ref, orbm_point_refkf (include/orbx_c.h): 8, 16 and 8 bytes
+OBSERVATION_DTYPE = np.dtype([("kf", "<u4"), ("desc_row", "<u4")])
+KEYFRAME_REF_DTYPE = np.dtype([("Ow", "<f4", (3,)), ("bad", "<u4")])
+POINT_REFKF_DTYPE = np.dtype([("kf", "<u4"), ("octave", "<i4")])
+assert (OBSERVATION_DTYPE.itemsize, KEYFRAME_REF_DTYPE.itemsize, POINT_REFKF_DTYPE.itemsize) == (8, 16, 8)
+ORBM_STATUS_REFRESH_SKIPPED = 128
 
 # orbm_map_point_proj (include/orbx_c.h), 24 bytes
 MAP_POINT_PROJ_DTYPE = np.dtype([("proj_x", "<f4"), ("proj_y", "<f4"), ("proj_xr", "<f4"), ("view_cos", "<f4"),

@@ -334,6 +334,32 @@ int launch_compact_in_view(const orbm_map_point_proj* proj, const uint8_t* mpdes
                            int frames, orbm_map_point_proj* c_proj, uint8_t* c_desc, int* c_map, int* c_nmp,
                            int c_pitch, int* err, void* stream);
 int launch_remap_out(int* out, const int* n, int kp_pitch, const int* c_map, int c_pitch, int frames, void* stream);
+// orbx_mappoint.hip — MapPoint::ComputeDistinctiveDescriptors and UpdateNormalAndDepth
+// for a list of points, in place on the device
+constexpr int kStatusRefreshSkipped = 128;  // matcher status bit: a point with an out-of-range kf, desc_row or octave
+constexpr int kRefreshClasses = 5;          // observation counts <= 8, <= 16, <= 32, <= 64, more
+struct RefreshArgs {
+  const orbm_observation* obs;
+  const uint32_t* off;  // points + 1
+  const uint32_t* ids;  // or null
+  int points;
+  const orbm_keyframe_ref* kfs;
+  uint32_t n_kfs;
+  const uint8_t* desc;
+  uint32_t desc_rows;
+  const orbm_point_refkf* ref;  // null with mps
+  float scale[kMaxLevels];
+  int nlevels;
+  orbm_map_point_world* mps;  // or null
+  uint8_t* mpdesc;            // or null
+  int* best;                  // or null
+  int* median;                // or null
+  int* err;                   // the handle's status word
+  int* counts;                // workspace: kRefreshClasses counters (8 ints)
+  int* lists;                 // workspace: kRefreshClasses x points point indices
+};
+size_t refresh_ws_bytes(int points);
+int launch_refresh_map_points(const RefreshArgs& A, void* stream);
 // orbx_triangulate.hip — SearchForTriangulation, one keyframe pair per workgroup
 struct TriSide {  // one side of the pairs; pitches of 0 share one keyframe across pairs
   const orbx_kp* kps;

@@ -2,8 +2,8 @@
 // its workspaces, the batch (device-array) entry points and the synchronous
 // host-array entry points staged through the handle's arena. The kernels are in
 // orbx_top2.hip, orbx_bow.hip, orbx_init.hip, orbx_stereo.hip,
-// orbx_project.hip, orbx_project_pose.hip, orbx_frustum.hip and
-// orbx_triangulate.hip.
+// orbx_project.hip, orbx_project_pose.hip, orbx_frustum.hip,
+// orbx_triangulate.hip and orbx_mappoint.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "orbx_internal.h"
+#include "orbx_mappoint.cuh"
 #include "orbx_posemath.cuh"
 
 using namespace orbx;
@@ -60,9 +61,12 @@ struct orbx_matcher {
   size_t pose_picks_cap = 0;
   uint8_t* view_ws = nullptr;  // SearchLocalPoints: isInFrustum records, then the points in view compacted
   size_t view_ws_bytes = 0;
+  uint8_t* refresh_ws = nullptr;  // RefreshMapPoints: class counters and work lists
+  size_t refresh_ws_bytes = 0;
   hipStream_t stream = nullptr;
-  WsOrder ws;  // stream order of cand / stereo_sad / pose_picks / view_ws / bow_* across caller streams
-  StreamMarks errm;  // streams of the launches that may set `err` (top-2, SearchByBoW, SearchLocalPoints)
+  WsOrder ws;  // stream order of cand / stereo_sad / pose_picks / view_ws / refresh_ws / bow_* across caller streams
+  // streams of the launches that may set `err` (top-2, SearchByBoW, SearchLocalPoints, RefreshMapPoints)
+  StreamMarks errm;
   // staging for the synchronous entry points
   void* stage = nullptr;
   size_t stage_bytes = 0;
@@ -237,6 +241,7 @@ int orbm_destroy(orbm_handle m) {
   if (m->bow_rec) (void)hipFree(m->bow_rec);
   if (m->pose_picks) (void)hipFree(m->pose_picks);
   if (m->view_ws) (void)hipFree(m->view_ws);
+  if (m->refresh_ws) (void)hipFree(m->refresh_ws);
   if (m->stage) (void)hipFree(m->stage);
   if (m->h_stage) (void)hipHostFree(m->h_stage);
   if (m->stream) (void)hipStreamDestroy(m->stream);
@@ -992,6 +997,143 @@ int orbm_search_local_points(orbm_handle m, const orbx_kp* kps, const uint8_t* d
   if (niv > kFrustumMaxView)
     return mfail(ORBX_ECAPACITY, "%d map points in view, more than %d can be searched", niv, kFrustumMaxView);
   *nmatches = nm;
+  return ORBX_OK;
+}
+
+// ------------- MapPoint::ComputeDistinctiveDescriptors, UpdateNormalAndDepth
+int orbm_distinctive_descriptor(const uint8_t* desc, int n, int* best, int* median) {
+  if (!best || n < 0 || (n && !desc)) return mfail(ORBX_EINVAL, "bad argument");
+  int best_i = -1, best_med = INT_MAX;
+  std::vector<uint32_t> w((size_t)n * 8);
+  if (n) memcpy(w.data(), desc, (size_t)n * 32);
+  const int at = (n - 1) >> 1;  // vDists[0.5*(N-1)] (src/MapPoint.cc:299)
+  for (int i = 0; i < n; ++i) {
+    int hist[257] = {0};
+    for (int j = 0; j < n; ++j) ++hist[mp_hamming(&w[(size_t)i * 8], &w[(size_t)j * 8])];
+    int med = 0;
+    for (int seen = hist[0]; seen <= at; seen += hist[med]) ++med;
+    if (med < best_med) {  // strictly smaller: the first row wins a tie (:301)
+      best_med = med;
+      best_i = i;
+    }
+  }
+  *best = best_i;
+  if (median) *median = n ? best_med : -1;
+  return ORBX_OK;
+}
+
+int orbm_update_normal_and_depth(const float* pos, const float* Ow_list, int n, const float* Ow_ref, float ref_scale,
+                                 float last_scale, float* normal_out, float* min_distance, float* max_distance) {
+  if (!pos || !Ow_ref || !normal_out || !min_distance || !max_distance || n < 0 || (n && !Ow_list))
+    return mfail(ORBX_EINVAL, "bad argument");
+  if (n == 0) return ORBX_OK;  // observations.empty() (src/MapPoint.cc:350)
+  float sum[3] = {0.f, 0.f, 0.f}, t[3], out[5];
+  for (int k = 0; k < n; ++k) {
+    mp_normal_term(pos, Ow_list + 3 * (size_t)k, t);
+    mp_normal_add(sum, t);
+  }
+  mp_finish(sum, (unsigned)n, pos, Ow_ref, ref_scale, last_scale, out);
+  normal_out[0] = out[0];
+  normal_out[1] = out[1];
+  normal_out[2] = out[2];
+  *min_distance = out[3];
+  *max_distance = out[4];
+  return ORBX_OK;
+}
+
+int orbm_refresh_map_points_batch(orbm_handle m, const orbm_observation* d_obs, const uint32_t* d_obs_off,
+                                  const uint32_t* d_point_ids, int points, const orbm_keyframe_ref* d_kfs, int n_kfs,
+                                  const uint8_t* d_desc, uint32_t desc_rows, const orbm_point_refkf* d_ref,
+                                  const float* scale, int nlevels, orbm_map_point_world* d_mps, uint8_t* d_mpdesc,
+                                  int* d_best, int* d_median, void* stream) {
+  if (!m || !d_obs || !d_obs_off || !d_kfs || !d_desc || points < 1 || n_kfs < 0)
+    return mfail(ORBX_EINVAL, "bad argument");
+  if (!d_mps && !d_mpdesc && !d_best && !d_median) return mfail(ORBX_EINVAL, "nothing to refresh: no output array");
+  if (d_mps && (!d_ref || !scale || nlevels < 1 || nlevels > kMaxLevels))
+    return mfail(ORBX_EINVAL, "records need d_ref and 1..%d scale factors", kMaxLevels);
+  if (((uintptr_t)d_desc | (uintptr_t)d_mpdesc) & 15) return mfail(ORBX_EINVAL, "descriptors must be 16-byte aligned");
+  MHIP(hipSetDevice(m->device));
+  hipStream_t s = (hipStream_t)stream;
+  if (m->ws.before(s)) return mfail(ORBX_EDEVICE, "stream wait on the workspace failed");
+  const size_t need = refresh_ws_bytes(points);
+  if (m->refresh_ws_bytes < need) {
+    if (m->ws.ev) MHIP(hipEventSynchronize(m->ws.ev));
+    if (m->refresh_ws) MHIP(hipFree(m->refresh_ws));
+    m->refresh_ws = nullptr;
+    m->refresh_ws_bytes = 0;
+    if (hipMalloc(&m->refresh_ws, need) != hipSuccess) return mfail(ORBX_ENOMEM, "map point refresh workspace");
+    m->refresh_ws_bytes = need;
+  }
+  RefreshArgs A{};
+  A.obs = d_obs;
+  A.off = d_obs_off;
+  A.ids = d_point_ids;
+  A.points = points;
+  A.kfs = d_kfs;
+  A.n_kfs = (uint32_t)n_kfs;
+  A.desc = d_desc;
+  A.desc_rows = desc_rows;
+  A.ref = d_mps ? d_ref : nullptr;
+  if (d_mps) std::memcpy(A.scale, scale, (size_t)nlevels * sizeof(float));
+  A.nlevels = d_mps ? nlevels : 0;
+  A.mps = d_mps;
+  A.mpdesc = d_mpdesc;
+  A.best = d_best;
+  A.median = d_median;
+  A.err = m->err;
+  A.counts = (int*)m->refresh_ws;
+  A.lists = (int*)(m->refresh_ws + 256);
+  if (launch_refresh_map_points(A, stream))
+    return mfail(ORBX_EDEVICE, "map point refresh launch: %s", hipGetErrorString(hipGetLastError()));
+  if (m->ws.after(s) || m->errm.mark(s)) return mfail(ORBX_EDEVICE, "event record failed");
+  return ORBX_OK;
+}
+
+int orbm_refresh_map_points(orbm_handle m, const orbm_observation* obs, const uint32_t* obs_off,
+                            const uint32_t* point_ids, int points, const orbm_keyframe_ref* kfs, int n_kfs,
+                            const uint8_t* desc, uint32_t desc_rows, const orbm_point_refkf* ref, const float* scale,
+                            int nlevels, orbm_map_point_world* mps, uint8_t* mpdesc, int n_mps, int* best,
+                            int* median) {
+  if (!m || !obs_off || points < 0 || n_kfs < 0 || n_mps < 0) return mfail(ORBX_EINVAL, "bad argument");
+  if (points == 0) return ORBX_OK;
+  if (!mps && !mpdesc && !best && !median) return mfail(ORBX_EINVAL, "nothing to refresh: no output array");
+  for (int p = 0; p < points; ++p)
+    if (obs_off[p + 1] < obs_off[p]) return mfail(ORBX_EINVAL, "obs_off descends at point %d", p);
+  const size_t nobs = obs_off[points];
+  if (nobs && (!obs || !kfs || !desc || !n_kfs || !desc_rows)) return mfail(ORBX_EINVAL, "null array");
+  if (mps || mpdesc) {
+    if (!point_ids && n_mps < points) return mfail(ORBX_EINVAL, "%d points in a table of %d", points, n_mps);
+    for (int p = 0; point_ids && p < points; ++p)
+      if (point_ids[p] >= (uint32_t)n_mps) return mfail(ORBX_EINVAL, "point id %u outside the table", point_ids[p]);
+  }
+  MHIP(hipSetDevice(m->device));
+  const size_t tab = std::max(n_mps, 1), nk = std::max(n_kfs, 1), nr = std::max<size_t>(desc_rows, 1);
+  int rc;
+  Stage st(m);
+  auto dobs = st.slot<orbm_observation>(std::max<size_t>(nobs, 1));
+  auto doff = st.slot<uint32_t>((size_t)points + 1);
+  auto dids = st.slot<uint32_t>(points);
+  auto dkf = st.slot<orbm_keyframe_ref>(nk);
+  auto dds = st.slot<uint8_t>(nr * 32);
+  auto drf = st.slot<orbm_point_refkf>(points);
+  auto dmp = st.slot<orbm_map_point_world>(tab);
+  auto dmd = st.slot<uint8_t>(tab * 32);
+  auto dbe = st.slot<int>(points);
+  auto dme = st.slot<int>(points);
+  if ((rc = st.reserve()) || (rc = st.up(dobs, obs, nobs)) || (rc = st.up(doff, obs_off, (size_t)points + 1)) ||
+      (rc = st.up(dids, point_ids, points)) || (rc = st.up(dkf, kfs, n_kfs)) ||
+      (rc = st.up(dds, desc, (size_t)desc_rows * 32)) || (rc = st.up(drf, ref, points)) ||
+      (rc = st.up(dmp, (const orbm_map_point_world*)mps, n_mps)) ||
+      (rc = st.up(dmd, (const uint8_t*)mpdesc, (size_t)n_mps * 32)) ||
+      (rc = orbm_refresh_map_points_batch(m, dobs, doff, point_ids ? (uint32_t*)dids : nullptr, points, dkf, n_kfs,
+                                          dds, desc_rows, ref ? (orbm_point_refkf*)drf : nullptr, scale, nlevels,
+                                          mps ? (orbm_map_point_world*)dmp : nullptr,
+                                          mpdesc ? (uint8_t*)dmd : nullptr, best ? (int*)dbe : nullptr,
+                                          median ? (int*)dme : nullptr, st.st)) ||
+      (mps && (rc = st.down(mps, dmp, n_mps))) || (mpdesc && (rc = st.down(mpdesc, dmd, (size_t)n_mps * 32))) ||
+      (best && (rc = st.down(best, dbe, points))) || (median && (rc = st.down(median, dme, points))) ||
+      (rc = st.finish()))
+    return rc;
   return ORBX_OK;
 }
 

@@ -18,6 +18,12 @@ Mirrors include/ORBmatcher.h:37-102 for the hot-path searches:
     nfound   = m.SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th)
     ORBmatcher.DescriptorDistance(a, b)
 
+for MapPoint::ComputeDistinctiveDescriptors / UpdateNormalAndDepth (src/MapPoint.cc:247-376):
+
+    best, median = m.RefreshMapPoints(obs, obs_off, kfs, desc, ref, scale, mps, mpdesc)  # both, a list of points
+    best, median = ComputeDistinctiveDescriptors(desc_rows)                               # one point, host
+    normal, min_d, max_d = UpdateNormalAndDepth(pos, Ow_list, Ow_ref, ref_scale, last_scale)
+
 and for the Frame constructors' tail (src/Frame.cc:118-227, 403-463, 642-663):
 
     F = ExtractRGBD(extractor, imGray, imDepth, K, distCoef, mbf, DepthMapFactor)  # one device round trip
@@ -384,6 +390,35 @@ class KeyFrame:
     @property
     def N(self) -> int:
         return len(self.mvKeysUn)
+
+
+def ComputeDistinctiveDescriptors(desc_rows) -> tuple:
+    """MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:277-306) on the gathered descriptors of
+    a point's observations ((n, 32) uint8, std::map order, bad keyframes left out): (best, median), the
+    first row with the least median distance to all rows and that median; (-1, -1) for no rows. Host only."""
+    d = np.ascontiguousarray(desc_rows, np.uint8).reshape(-1, 32)
+    best, med = C.c_int(-1), C.c_int(-1)
+    check(lib().orbm_distinctive_descriptor(ptr(d) if len(d) else None, len(d), C.byref(best), C.byref(med)),
+          matcher=True)
+    return best.value, med.value
+
+
+def UpdateNormalAndDepth(pos, Ow_list, Ow_ref, ref_scale: float, last_scale: float):
+    """MapPoint::UpdateNormalAndDepth (src/MapPoint.cc:353-375): (mNormalVector, mfMinDistance,
+    mfMaxDistance) from mWorldPos, the observing keyframes' camera centres ((n, 3), std::map order), the
+    reference keyframe's centre, mvScaleFactors[level] there and mvScaleFactors[nLevels-1]; None for no
+    observations (the reference returns untouched). Host only."""
+    pos = np.ascontiguousarray(pos, np.float32).reshape(3)
+    ow = np.ascontiguousarray(Ow_list, np.float32).reshape(-1, 3)
+    owr = np.ascontiguousarray(Ow_ref, np.float32).reshape(3)
+    if len(ow) == 0:
+        return None
+    normal = np.zeros(3, np.float32)
+    mn, mx = C.c_float(0), C.c_float(0)
+    check(lib().orbm_update_normal_and_depth(ptr(pos), ptr(ow), len(ow), ptr(owr), C.c_float(ref_scale),
+                                             C.c_float(last_scale), ptr(normal), C.byref(mn), C.byref(mx)),
+          matcher=True)
+    return normal, np.float32(mn.value), np.float32(mx.value)
 
 
 def _mp_mask(a) -> np.ndarray:
@@ -757,6 +792,33 @@ class ORBmatcher:
         self.last_projection = o.copy()
         self.last_frustum = proj
         return nm.value, proj["track_in_view"] != 0
+
+    def RefreshMapPoints(self, obs, obs_off, kfs, desc, ref=None, scale=None, mps=None, mpdesc=None,
+                         point_ids=None):
+        """ComputeDistinctiveDescriptors + UpdateNormalAndDepth for a list of points in one device round
+        trip (orbm_refresh_map_points). obs: OBSERVATION_DTYPE entries, point p's at obs_off[p] ..
+        obs_off[p+1] in std::map order; kfs: KEYFRAME_REF_DTYPE table; desc: (rows, 32) descriptor arena;
+        ref: POINT_REFKF_DTYPE per point and scale = mvScaleFactors (with mps); mps: MAP_POINT_WORLD_DTYPE
+        table and mpdesc: (len, 32) descriptors, both updated in place at row point_ids[p] (default p);
+        either may be None. Returns (best, median) per point, -1 where no descriptor was chosen. Points
+        skipped for an out-of-range entry set bit 128 of status()."""
+        obs = np.ascontiguousarray(obs, _lib.OBSERVATION_DTYPE)
+        off = np.ascontiguousarray(obs_off, np.uint32)
+        kfs = np.ascontiguousarray(kfs, _lib.KEYFRAME_REF_DTYPE)
+        desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        points = len(off) - 1
+        ids = None if point_ids is None else np.ascontiguousarray(point_ids, np.uint32)
+        rf = None if ref is None else np.ascontiguousarray(ref, _lib.POINT_REFKF_DTYPE)
+        sc = None if scale is None else np.ascontiguousarray(scale, np.float32)
+        for a, dt in ((mps, MAP_POINT_WORLD_DTYPE), (mpdesc, np.uint8)):
+            if a is not None and not (isinstance(a, np.ndarray) and a.dtype == dt and a.flags.c_contiguous):
+                raise _lib.OrbxError(_lib.ORBX_EINVAL, "mps / mpdesc must be contiguous arrays updated in place")
+        n_mps = len(mps) if mps is not None else (len(mpdesc.reshape(-1, 32)) if mpdesc is not None else 0)
+        best, med = np.full(max(points, 1), -1, np.int32), np.full(max(points, 1), -1, np.int32)
+        check(lib().orbm_refresh_map_points(
+            self._h, ptr(obs), ptr(off), ptr(ids), points, ptr(kfs), len(kfs), ptr(desc), len(desc), ptr(rf), ptr(sc),
+            0 if sc is None else len(sc), ptr(mps), ptr(mpdesc), n_mps, ptr(best), ptr(med)), matcher=True)
+        return best[:points], med[:points]
 
     def SearchByBoW(self, A: KeyFrame, B, out: list | None = None) -> int:
         """KF-Frame (B is a Frame) or KF-KF (B is a KeyFrame). Fills `out` with matched
