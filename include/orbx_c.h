@@ -49,6 +49,14 @@
  *                          UndistortKeyPoints + ComputeStereoFromRGBD,
  *                          src/Frame.cc:134-144 (no depth: the monocular
  *                          constructor's :189-197)
+ *   orbx_rectify_maps      cv::initUndistortRectifyMap(K, D, R, P.rowRange(0,3)
+ *                          .colRange(0,3), size, CV_32F, M1, M2)
+ *                          Examples/Stereo/stereo_euroc.cc:97-98,
+ *                          Examples/ROS/ROS_WS/src/stereo/src/ros_stereo.cc:106-107
+ *   orbx_remap_host / orbx_rectify_create / orbx_rectify_batch / orbx_set_rectify
+ *                          cv::remap(im, imRect, M1, M2, cv::INTER_LINEAR) on the
+ *                          left and the right image before TrackStereo,
+ *                          stereo_euroc.cc:136-137, ros_stereo.cc:161-162
  *   orbm_search_by_projection  ORBmatcher::SearchByProjection(Frame&,
  *                          const vector<MapPoint*>&, th)  include/ORBmatcher.h:48,
  *                          src/ORBmatcher.cc:45-126 (Tracking::SearchLocalPoints)
@@ -894,6 +902,66 @@ int orbx_frame_tail_batch(const orbx_calib* calib, const orbx_kp* d_kps, const i
 int orbx_rgbd_frame(orbx_handle h, const uint8_t* img, size_t stride, const void* depth_img, int depth_type,
                     size_t depth_stride, int w, int h_, const orbx_calib* calib, float depth_factor, float mbf,
                     orbx_kp* kps, int cap, uint8_t* desc, int* n, orbx_kp* kps_un, float* uRight, float* depth);
+
+/* ------------------------------------- stereo rectification ahead of ExtractORB
+ * What the stereo examples do to every camera pair before TrackStereo
+ * (Examples/Stereo/stereo_euroc.cc:97-98,136-137; Examples/ROS/ROS_WS/src/
+ * stereo/src/ros_stereo.cc:106-107,161-162): two pairs of float maps from
+ * cv::initUndistortRectifyMap once, then cv::remap(im, imRect, M1, M2,
+ * cv::INTER_LINEAR) on the left and the right image of every frame. Both are
+ * restated here; no side of a source or destination
+ * image may exceed 32766 (ORBX_EINVAL). */
+
+/* cv::initUndistortRectifyMap(K, D, R, P.rowRange(0,3).colRange(0,3),
+ * cv::Size(w, h), CV_32F, M1, M2) (stereo_euroc.cc:97-98, ros_stereo.cc:
+ * 106-107) of OpenCV 3.x, in double: K, R row-major 3x3 (LEFT.K, LEFT.R), D =
+ * k1 k2 p1 p2 k3 (LEFT.D), P row-major 3x4 of which columns 0..2 are used
+ * (LEFT.P); map1 (x) and map2 (y): w*h floats each, rows of w. Host only. */
+int orbx_rectify_maps(const double K[9], const double D[5], const double R[9], const double P[12], int w, int h,
+                      float* map1, float* map2);
+
+/* cv::remap(src, dst, map1, map2, cv::INTER_LINEAR) (stereo_euroc.cc:136-137,
+ * ros_stereo.cc:161-162) for an 8-bit single-channel image, CV_32FC1 maps of
+ * dst_w x dst_h (rows of dst_w floats) and BORDER_CONSTANT 0, on the host: the
+ * function the kernels evaluate. Host only. */
+int orbx_remap_host(const uint8_t* src, int src_w, int src_h, size_t src_stride, const float* map1,
+                    const float* map2, int dst_w, int dst_h, uint8_t* dst, size_t dst_stride);
+
+/* One camera's remap (the M1, M2 pair of stereo_euroc.cc:97-98), prepared
+ * once on `device` from host maps of dst_w x dst_h for sources of src_w x
+ * src_h: the per-frame kernel reads 4 bytes per output pixel (8 when a source
+ * side exceeds 2046) instead of the two float maps. Synchronous. */
+typedef struct orbx_rectifier* orbx_rectify_handle;
+int orbx_rectify_create(int device, const float* map1, const float* map2, int dst_w, int dst_h, int src_w,
+                        int src_h, orbx_rectify_handle* out);
+/* Not while an extractor still has it set (orbx_set_rectify) or a batch call
+ * on it is in flight. */
+int orbx_rectify_destroy(orbx_rectify_handle r);
+
+/* cv::remap (stereo_euroc.cc:136-137) for `batch` device-resident frames,
+ * asynchronous on `stream`: frame i of src_w x src_h at d_src +
+ * i*src_frame_pitch with rows src_stride apart, its rectification of dst_w x
+ * dst_h to d_dst + i*dst_frame_pitch with rows dst_stride apart: the layout
+ * orbx_extract_batch reads. Only bytes [0, src_w) of a source row are read and
+ * only bytes [0, dst_w) of a destination row written. Equal to
+ * orbx_remap_host byte for byte. */
+int orbx_rectify_batch(orbx_rectify_handle r, const uint8_t* d_src, size_t src_stride, size_t src_frame_pitch,
+                       uint8_t* d_dst, size_t dst_stride, size_t dst_frame_pitch, int batch, void* stream);
+
+/* While r is set on h (NULL clears it), every host-image call on h
+ * (orbx_extract, orbx_rgbd_frame, h's side of orbm_stereo_frame) takes `img`
+ * as the raw camera image and extracts from its rectification, as
+ * stereo_euroc.cc:136-137 does with cv::remap before TrackStereo: the raw
+ * image is uploaded to a second device buffer, the remap kernel writes the
+ * handle's frame buffer and the extraction follows, on the handle's stream
+ * and inside the call's captured graph (still one linear chain). The
+ * rectifier's source and destination size must both equal the call's w x h
+ * (ORBX_EINVAL from that call otherwise) and r must live on h's device.
+ * orbx_get_level(h, 0, 0, 0, ...) after such a call returns the rectified
+ * image, and so does level 0 of the host pyramid. orbx_extract_batch is not
+ * affected (rectify its frames with orbx_rectify_batch). The caller keeps r
+ * alive while it is set. */
+int orbx_set_rectify(orbx_handle h, orbx_rectify_handle r);
 
 /* ------------------------------------------------------ vocabulary (DBoW2) */
 typedef struct orbv_vocabulary* orbv_handle;

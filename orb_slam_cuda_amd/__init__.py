@@ -12,8 +12,10 @@ from .matcher import (ComputeDistinctiveDescriptors, ComputeImageBounds, Compute
                       MapPoints, ORBmatcher, UndistortKeyPoints, UpdateNormalAndDepth)
 from .vocabulary import ComputeBoW, ORBVocabulary  # noqa: F401
 from .database import KeyFrameDatabase  # noqa: F401
+from .rectify import Rectifier, StereoRectifier  # noqa: F401
 
 __all__ = ["ORBextractor", "ORBmatcher", "ORBVocabulary", "Frame", "KeyFrame", "ComputeBoW", "KeyFrameDatabase",
            "ComputeStereoMatches", "ComputeStereoMatchesLast", "ExtractStereo", "MapPoints", "KP_DTYPE", "OrbxError",
            "device_count", "header_functions", "lib", "UndistortKeyPoints", "ComputeImageBounds",
-           "ComputeStereoFromRGBD", "ExtractRGBD", "ComputeDistinctiveDescriptors", "UpdateNormalAndDepth"]
+           "ComputeStereoFromRGBD", "ExtractRGBD", "ComputeDistinctiveDescriptors", "UpdateNormalAndDepth", "Rectifier",
+           "StereoRectifier"]

@@ -317,6 +317,15 @@ def lib() -> C.CDLL:
             C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_size_t, C.c_int, C.c_int,
             C.POINTER(OrbxCalib), C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int),
             C.c_void_p, C.c_void_p, C.c_void_p]
+        L.orbx_rectify_maps.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.orbx_remap_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int,
+                                      C.c_int, C.c_void_p, C.c_size_t]
+        L.orbx_rectify_create.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.POINTER(C.c_void_p)]
+        L.orbx_rectify_destroy.argtypes = [C.c_void_p]
+        L.orbx_rectify_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t,
+                                         C.c_size_t, C.c_int, C.c_void_p]
+        L.orbx_set_rectify.argtypes = [C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 

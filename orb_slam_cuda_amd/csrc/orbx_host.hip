@@ -162,6 +162,10 @@ struct orbx_extractor {
   size_t h_depth_bytes = 0, h_tail_bytes = 0;
   hipStream_t dstream = nullptr;
   hipEvent_t dev = nullptr;  // depth upload done
+  // orbx_set_rectify: while set, the staged image is the raw camera image; it
+  // is uploaded to d_raw and the remap kernel writes d_in ahead of the pyramid
+  orbx_rectifier* rect = nullptr;
+  DeviceBuf d_raw;
   // ORBX_EXTRACT_PROF=1 (diagnostics): orbx_extract's host phases per call
   // (s), their medians printed by orbx_destroy: staging copy, issue, wait, copy-out
   std::vector<float> prof_t[4];
@@ -1211,10 +1215,21 @@ static size_t host_pyr_layout(orbx_extractor* h) {
 static int issue_one_frame(orbx_extractor* h, size_t pitch, int hh, int cap_frame) {
   hipStream_t s = h->stream;
   const ExtractParams& P = h->plan.P;
-  HIP_OK(hipMemcpyAsync(h->d_in.p, h->h_in, pitch * hh, hipMemcpyHostToDevice, s));
+  if (h->rect) {
+    // the raw image to its own buffer, its rectification into the frame buffer
+    HIP_OK(hipMemcpyAsync(h->d_raw.p, h->h_in, pitch * hh, hipMemcpyHostToDevice, s));
+    if (launch_rectify(*h->rect, h->d_raw.as<uint8_t>(), pitch, pitch * hh, h->d_in.as<uint8_t>(), pitch, pitch * hh, 1,
+                       s))
+      return fail(ORBX_EDEVICE, "remap launch failed: %s", hipGetErrorString(hipGetLastError()));
+  } else {
+    HIP_OK(hipMemcpyAsync(h->d_in.p, h->h_in, pitch * hh, hipMemcpyHostToDevice, s));
+  }
   uint8_t* d = h->d_out.as<uint8_t>();
   const size_t doff = out_desc_off(cap_frame);
   const bool hp = h->host_pyr && P.L > 1;
+  // level 0 of the host pyramid is the pinned staging: with a rectifier the
+  // rectified image is copied back over the raw one (uploaded by then)
+  const bool hp0 = h->host_pyr && h->rect;
   const int rc = launch_extract(P, buffers_of(h->plan), h->d_in.as<uint8_t>(), 1, pitch * hh, pitch,
                                 (orbx_kp*)(d + 16), d + doff, (int*)d, s, h->timing ? (void**)h->ev : nullptr,
                                 hp ? (void*)h->pev[0] : nullptr, (int*)d + 1, h->order);
@@ -1232,7 +1247,10 @@ static int issue_one_frame(orbx_extractor* h, size_t pitch, int hh, int cap_fram
         HIP_OK(hipMemcpyAsync(hpyr + h->h_pyr_off[l], pyr + P.lv[l].off, (size_t)P.lv[l].plane,
                               hipMemcpyDeviceToHost, h->pstream));
     }
+    if (hp0) HIP_OK(hipMemcpyAsync(h->h_in, h->d_in.p, pitch * hh, hipMemcpyDeviceToHost, h->pstream));
     HIP_OK(hipEventRecord(h->pev[1], h->pstream));
+  } else if (hp0) {
+    HIP_OK(hipMemcpyAsync(h->h_in, h->d_in.p, pitch * hh, hipMemcpyDeviceToHost, s));
   }
   // count, status word (bytes 4..7 of the block's header, written there by
   // the last stage), keypoints and descriptors in one copy
@@ -1253,6 +1271,10 @@ static int issue_one_frame(orbx_extractor* h, size_t pitch, int hh, int cap_fram
 static int extract_prepare(orbx_extractor* h, const uint8_t* img, int w, int hh, size_t stride) {
   h->last_empty = false;
   if (!img || w < 0 || hh < 0 || stride < (size_t)w) return fail(ORBX_EINVAL, "bad image");
+  if (const orbx_rectifier* r = h->rect)
+    if (r->src_w != w || r->src_h != hh || r->dst_w != w || r->dst_h != hh)
+      return fail(ORBX_EINVAL, "the handle's rectifier maps %d x %d to %d x %d, the image is %d x %d", r->src_w, r->src_h,
+                  r->dst_w, r->dst_h, w, hh);
   HIP_OK(hipSetDevice(h->cfg.device));
   if (w != h->plan.W || hh != h->plan.H) {
     // the reference accepts any image size per call: re-plan for it (after
@@ -1279,6 +1301,10 @@ static int extract_prepare(orbx_extractor* h, const uint8_t* img, int w, int hh,
   if (h->d_out.n < out_bytes) {
     drop_graph();
     if ((rc = h->d_out.alloc(out_bytes))) return rc;
+  }
+  if (h->rect && h->d_raw.n < pitch * hh) {
+    drop_graph();
+    if ((rc = h->d_raw.alloc(pitch * hh))) return rc;
   }
   if (h->h_in_bytes < pitch * hh || h->h_out_bytes < out_bytes) drop_graph();
   if ((rc = host_reserve(&h->h_in, &h->h_in_bytes, pitch * hh)) ||
@@ -1589,6 +1615,85 @@ int orbx_rgbd_frame(orbx_handle h, const uint8_t* img, size_t stride, const void
     if (uRight) std::fill(uRight, uRight + cnt, -1.f);
     if (depth) std::fill(depth, depth + cnt, -1.f);
   }
+  return ORBX_OK;
+}
+
+// ------------------------------------------- stereo rectification (orbx_rectify.hip)
+static bool remap_side_ok(int v) { return v >= 1 && v <= 32766; }
+
+int orbx_rectify_maps(const double K[9], const double D[5], const double R[9], const double P[12], int w, int hh,
+                      float* map1, float* map2) {
+  if (!K || !D || !R || !P || !map1 || !map2) return fail(ORBX_EINVAL, "orbx_rectify_maps: null argument");
+  if (!remap_side_ok(w) || !remap_side_ok(hh))
+    return fail(ORBX_EINVAL, "orbx_rectify_maps: size %d x %d outside 1 .. 32766", w, hh);
+  rectify_maps_host(K, D, R, P, w, hh, map1, map2);
+  return ORBX_OK;
+}
+
+int orbx_remap_host(const uint8_t* src, int src_w, int src_h, size_t src_stride, const float* map1,
+                    const float* map2, int dst_w, int dst_h, uint8_t* dst, size_t dst_stride) {
+  if (!src || !map1 || !map2 || !dst) return fail(ORBX_EINVAL, "orbx_remap_host: null argument");
+  if (!remap_side_ok(src_w) || !remap_side_ok(src_h) || !remap_side_ok(dst_w) || !remap_side_ok(dst_h))
+    return fail(ORBX_EINVAL, "orbx_remap_host: %d x %d to %d x %d: a side outside 1 .. 32766", src_w, src_h, dst_w,
+                dst_h);
+  if (src_stride < (size_t)src_w || dst_stride < (size_t)dst_w)
+    return fail(ORBX_EINVAL, "orbx_remap_host: a row stride below its width");
+  remap_host(src, src_w, src_h, src_stride, map1, map2, dst_w, dst_h, dst, dst_stride);
+  return ORBX_OK;
+}
+
+int orbx_rectify_create(int device, const float* map1, const float* map2, int dst_w, int dst_h, int src_w,
+                        int src_h, orbx_rectify_handle* out) {
+  if (!map1 || !map2 || !out) return fail(ORBX_EINVAL, "orbx_rectify_create: null argument");
+  if (!remap_side_ok(src_w) || !remap_side_ok(src_h) || !remap_side_ok(dst_w) || !remap_side_ok(dst_h))
+    return fail(ORBX_EINVAL, "orbx_rectify_create: %d x %d to %d x %d: a side outside 1 .. 32766", src_w, src_h, dst_w,
+                dst_h);
+  const int rc = rectifier_create(device, map1, map2, dst_w, dst_h, src_w, src_h, out);
+  if (rc) return fail(rc, "orbx_rectify_create: %s", hipGetErrorString(hipGetLastError()));
+  return ORBX_OK;
+}
+
+int orbx_rectify_destroy(orbx_rectify_handle r) {
+  if (!r) return ORBX_OK;
+  (void)hipSetDevice(r->device);
+  rectifier_destroy(r);
+  return ORBX_OK;
+}
+
+int orbx_rectify_batch(orbx_rectify_handle r, const uint8_t* d_src, size_t src_stride, size_t src_frame_pitch,
+                       uint8_t* d_dst, size_t dst_stride, size_t dst_frame_pitch, int batch, void* stream) {
+  if (!r) return fail(ORBX_EINVAL, "orbx_rectify_batch: null rectifier");
+  if (batch < 0) return fail(ORBX_EINVAL, "orbx_rectify_batch: negative batch");
+  if (batch == 0) return ORBX_OK;
+  if (!d_src || !d_dst) return fail(ORBX_EINVAL, "orbx_rectify_batch: null image");
+  if (src_stride < (size_t)r->src_w || dst_stride < (size_t)r->dst_w)
+    return fail(ORBX_EINVAL, "orbx_rectify_batch: row strides %zu / %zu below the widths %d / %d", src_stride,
+                dst_stride, r->src_w, r->dst_w);
+  // the last row of a frame needs its width only
+  if (batch > 1 && (src_frame_pitch < src_stride * (size_t)(r->src_h - 1) + r->src_w ||
+                    dst_frame_pitch < dst_stride * (size_t)(r->dst_h - 1) + r->dst_w))
+    return fail(ORBX_EINVAL, "orbx_rectify_batch: a frame pitch below one frame");
+  HIP_OK(hipSetDevice(r->device));
+  if (launch_rectify(*r, d_src, src_stride, src_frame_pitch, d_dst, dst_stride, dst_frame_pitch, batch,
+                     (hipStream_t)stream))
+    return fail(ORBX_EDEVICE, "remap launch failed: %s", hipGetErrorString(hipGetLastError()));
+  return ORBX_OK;
+}
+
+int orbx_set_rectify(orbx_handle h, orbx_rectify_handle r) {
+  if (!h) return fail(ORBX_EINVAL, "null handle");
+  if (r && r->device != h->cfg.device)
+    return fail(ORBX_EINVAL, "orbx_set_rectify: the rectifier is on device %d, the extractor on %d", r->device,
+                h->cfg.device);
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (h->rect == r) return ORBX_OK;
+  // the single-frame graph was captured with the old setting (the calls that
+  // replay it have all returned); the next call runs plain, the one after captures
+  if (h->ws.ev) (void)hipEventSynchronize(h->ws.ev);
+  if (h->graph) (void)hipGraphExecDestroy(h->graph);
+  h->graph = nullptr;
+  h->warm_w = h->warm_h = 0;
+  h->rect = r;
   return ORBX_OK;
 }
 

@@ -498,4 +498,27 @@ int launch_frame_tail(const FrameTailParams& P, const orbx_kp* kps, const int* c
 void undistort_points_host(const orbx_calib& c, const float* xy, int n, float* xy_out);
 void image_bounds_host(const orbx_calib& c, int w, int h, orbm_grid_bounds* out);
 
+// orbx_rectify.hip: cv::initUndistortRectifyMap and cv::remap (INTER_LINEAR,
+// BORDER_CONSTANT 0, 8-bit) on the host, a rectifier's prepared map and the
+// per-frame kernel: frame f of `batch` from src + f*src_fpitch (src_w x src_h,
+// rows src_stride apart) to dst + f*dst_fpitch (dst_w x dst_h)
+void rectify_maps_host(const double* K, const double* D, const double* R, const double* P, int w, int h, float* map1,
+                       float* map2);
+void remap_host(const uint8_t* src, int src_w, int src_h, size_t src_stride, const float* map1, const float* map2,
+                int dst_w, int dst_h, uint8_t* dst, size_t dst_stride);
+int rectifier_create(int device, const float* map1, const float* map2, int dst_w, int dst_h, int src_w, int src_h,
+                     orbx_rectifier** out);
+void rectifier_destroy(orbx_rectifier* r);
+int launch_rectify(const orbx_rectifier& r, const uint8_t* src, size_t src_stride, size_t src_fpitch, uint8_t* dst,
+                   size_t dst_stride, size_t dst_fpitch, int batch, hipStream_t stream);
+
 }  // namespace orbx
+
+// One camera's rectification (orbx_rectify_create): the prepared map on the
+// device, `mpitch` records of rec_bytes (4 or 8) per destination row.
+struct orbx_rectifier {
+  int device;
+  int dst_w, dst_h, src_w, src_h;
+  int rec_bytes, mpitch;
+  void* recs;
+};

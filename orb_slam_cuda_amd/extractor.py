@@ -101,6 +101,13 @@ class ORBextractor:
                                      None, 2**31 - 1, None, C.byref(n)))
         return self.frame_capacity
 
+    def set_rectify(self, rectifier=None) -> None:
+        """While a rectify.Rectifier is set, every image given to this extractor is the
+        raw camera image and the extraction runs on its rectification (orbx_set_rectify);
+        None clears it. The extractor keeps the rectifier alive."""
+        check(lib().orbx_set_rectify(self._h, rectifier.handle if rectifier is not None else None))
+        self._rectifier = rectifier
+
     def set_stage_order(self, order: str) -> None:
         """The stages' launch order for later extractions (orbx_set_stage_order)."""
         check(lib().orbx_set_stage_order(self._h, order.encode()))

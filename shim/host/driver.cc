@@ -11,6 +11,10 @@
 //   orbx_shim_driver --scene SCENE.bin OUT.bin   (one ORBmatcher method on a test scene, scene.cc)
 //   orbx_shim_driver --stereo LEFT.u8 RIGHT.u8 NPAIRS W H BF OUTDIR
 //                                 (stereo Frames, two extraction threads each, + ComputeStereoMatches)
+//   orbx_shim_driver --stereo-rectify LEFT.u8 RIGHT.u8 M1L.f32 M2L.f32 M1R.f32 M2R.f32 NPAIRS W H BF OUTDIR
+//                                 (the same on raw camera pairs: the two extractors rectify them through the
+//                                 W x H float maps, ORBextractor::SetRectification, as stereo_euroc.cc:136-137's
+//                                 cv::remap calls would)
 //   orbx_shim_driver --latency MONO.u8 LEFT.u8 RIGHT.u8 NFRAMES W H NCALLS WARM
 //                                 (per-call host times of the drop-in path, one JSON line)
 //   orbx_shim_driver --rgbd GRAY.u8 DEPTH.raw u16|f32 W H NFEATURES fx,fy,cx,cy,k1,k2,p1,p2[,k3] BF DEPTHMAPFACTOR OUTDIR
@@ -59,8 +63,9 @@ int run_scene_latency(const std::string& in, int ncalls, int warm);  // scene.cc
 // and right extraction on two std::threads as the reference's :77-80, then
 // ComputeStereoMatches); writes each
 // pair's left / right keypoints, mvuRight and mvDepth.
+// maps (--stereo-rectify): the files of M1l, M2l, M1r, M2r; the images are then raw camera pairs.
 static int run_stereo(const char* left, const char* right, int npairs, int W, int H, float bf,
-                      const std::string& out) {
+                      const std::string& out, const char* const* maps = nullptr) {
   const size_t plane = (size_t)W * H;
   std::vector<uint8_t> L(plane * npairs), R(plane * npairs);
   for (auto& lr : {std::make_pair(left, &L), std::make_pair(right, &R)}) {
@@ -72,6 +77,21 @@ static int run_stereo(const char* left, const char* right, int npairs, int W, in
     fclose(f);
   }
   ORBextractor left_ext(2000, 1.2f, 8, 20, 7, W, H), right_ext(2000, 1.2f, 8, 20, 7, W, H);
+  if (maps) {
+    std::vector<float> m[4];
+    for (int k = 0; k < 4; ++k) {
+      m[k].resize(plane);
+      FILE* f = fopen(maps[k], "rb");
+      const bool ok = f && fread(m[k].data(), 4, plane, f) == plane;
+      if (f) fclose(f);
+      if (!ok) {
+        fprintf(stderr, "cannot read %s\n", maps[k]);
+        return 2;
+      }
+    }
+    left_ext.SetRectification(cv::Mat(H, W, CV_32F, m[0].data()), cv::Mat(H, W, CV_32F, m[1].data()));
+    right_ext.SetRectification(cv::Mat(H, W, CV_32F, m[2].data()), cv::Mat(H, W, CV_32F, m[3].data()));
+  }
   // Frame::fx from K (src/Frame.cc:103-108): the KITTI calibration
   Frame::fx = 718.856f;
   Frame::fy = 718.856f;
@@ -343,6 +363,9 @@ int main(int argc, char** argv) {
                          atoi(argv[9]));
     if (argc == 9 && std::string(argv[1]) == "--stereo")
       return run_stereo(argv[2], argv[3], atoi(argv[4]), atoi(argv[5]), atoi(argv[6]), (float)atof(argv[7]), argv[8]);
+    if (argc == 13 && std::string(argv[1]) == "--stereo-rectify")
+      return run_stereo(argv[2], argv[3], atoi(argv[8]), atoi(argv[9]), atoi(argv[10]), (float)atof(argv[11]), argv[12],
+                        argv + 4);
     if (argc == 12 && std::string(argv[1]) == "--rgbd")
       return run_rgbd(argv[2], argv[3], argv[4], atoi(argv[5]), atoi(argv[6]), atoi(argv[7]), argv[8],
                       (float)atof(argv[9]), (float)atof(argv[10]), argv[11]);
@@ -354,8 +377,9 @@ int main(int argc, char** argv) {
     fprintf(stderr,
             "usage: %s FRAMES.u8 NFRAMES W H VOC.txt|- OUTDIR\n"
             "       %s --rgbd GRAY.u8 DEPTH.raw u16|f32 W H NFEATURES fx,fy,cx,cy,k1,k2,p1,p2[,k3] BF DEPTHMAPFACTOR "
-            "OUTDIR\n",
-            argv[0], argv[0]);
+            "OUTDIR\n"
+            "       %s --stereo-rectify LEFT.u8 RIGHT.u8 M1L.f32 M2L.f32 M1R.f32 M2R.f32 NPAIRS W H BF OUTDIR\n",
+            argv[0], argv[0], argv[0]);
     return 1;
   }
   const std::string out = argv[6];

@@ -78,6 +78,15 @@ class ORBextractor {
                    float mbf, std::vector<cv::KeyPoint>& keys, cv::OutputArray descriptors,
                    std::vector<cv::KeyPoint>& keysUn, std::vector<float>& uRight, std::vector<float>& depth);
 
+  // The per-camera pair of maps of the stereo examples (M1l, M2l of
+  // Examples/Stereo/stereo_euroc.cc:97, CV_32F from cv::initUndistortRectifyMap):
+  // from now on every image given to this extractor is the raw camera image
+  // and the extraction runs on cv::remap(image, ., M1, M2, cv::INTER_LINEAR),
+  // computed on the device ahead of the pyramid (orbx_set_rectify), which
+  // replaces the example's cv::remap call (:136-137). Images must have the
+  // maps' size. Two empty Mats clear it.
+  void SetRectification(const cv::Mat& M1, const cv::Mat& M2);
+
   int inline GetLevels() { return nlevels; }
   float inline GetScaleFactor() { return (float)scaleFactor; }
   std::vector<float> inline GetScaleFactors() { return mvScaleFactor; }
@@ -131,6 +140,7 @@ class ORBextractor {
   void EndCall(int n, std::vector<cv::KeyPoint>& keypoints, cv::OutputArray descriptors);
 
   orbx_handle h_ = nullptr;
+  orbx_rectify_handle rect_ = nullptr;  // SetRectification
   int cap_ = 0;
   bool timing_ = false;
   bool host_pyr_ = true;

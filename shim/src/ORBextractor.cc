@@ -92,6 +92,26 @@ ORBextractor::~ORBextractor() {
     }
   }
   if (h_) orbx_destroy(h_);
+  if (rect_) orbx_rectify_destroy(rect_);
+}
+
+void ORBextractor::SetRectification(const cv::Mat& M1, const cv::Mat& M2) {
+  orbx_rectify_handle next = nullptr;
+  if (!M1.empty() || !M2.empty()) {
+    if (M1.type() != CV_32F || M2.type() != CV_32F || M1.rows != M2.rows || M1.cols != M2.cols)
+      throw std::runtime_error("SetRectification: M1 and M2 must be CV_32F maps of one size");
+    const cv::Mat m1 = M1.isContinuous() ? M1 : M1.clone(), m2 = M2.isContinuous() ? M2 : M2.clone();
+    const char* dev = getenv("ORBX_DEVICE");
+    orbx_check(orbx_rectify_create(dev ? atoi(dev) : 0, m1.ptr<float>(), m2.ptr<float>(), M1.cols, M1.rows, M1.cols,
+                                   M1.rows, &next));
+  }
+  const int rc = orbx_set_rectify(h_, next);
+  if (rc) {
+    if (next) orbx_rectify_destroy(next);
+    orbx_check(rc);
+  }
+  if (rect_) orbx_rectify_destroy(rect_);
+  rect_ = next;
 }
 
 // Before a call: outputs sized to the capacity (keypoints and descriptors are
