@@ -81,6 +81,8 @@
  *   orbm_search_by_projection_pose_batch  all of the above, batched on device
  *   orbm_search_for_triangulation  ORBmatcher::SearchForTriangulation
  *                          include/ORBmatcher.h:72, src/ORBmatcher.cc:657-823
+ *   orbm_pose_optimization / _batch / _host  Optimizer::PoseOptimization(Frame*)
+ *                          include/Optimizer.h:53, src/Optimizer.cc:334-543
  *   orbv_load_text / orbv_create  ORBVocabulary::loadFromTextFile
  *                          (DBoW2 TemplatedVocabulary, include/ORBVocabulary.h:30,
  *                          Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1338-1418)
@@ -303,7 +305,9 @@ int orbm_destroy(orbm_handle m);
  * orbm_search_local_points_batch found more than 8192 map points in view in
  * a frame, the points in view after the first 8192 were not searched; bit
  * 128: orbm_refresh_map_points_batch / orbm_refresh_map_points skipped a
- * point whose list names a keyframe, descriptor row or octave out of range).
+ * point whose list names a keyframe, descriptor row or octave out of range;
+ * bit 256: orbm_pose_optimization_batch / orbm_pose_optimization left out a
+ * keypoint whose octave or map point row is out of range).
  * SearchForInitialization keeps no
  * candidate lists (8 smallest keys per query) and never sets it. Waits for
  * the matcher's own launches that may set it (on whatever streams they ran),
@@ -736,6 +740,78 @@ int orbm_refresh_map_points(orbm_handle m, const orbm_observation* obs, const ui
                             const orbm_point_refkf* ref, const float* scale, int nlevels,
                             orbm_map_point_world* mps, uint8_t* mpdesc, int n_mps, int* best,
                             int* median);
+
+/* ------------------------------------------- Optimizer::PoseOptimization
+ * The per-frame pose solve of Tracking (src/Optimizer.cc:334-543) between
+ * SearchByProjection and SearchLocalPoints: one SE3 vertex, a monocular
+ * (mvuRight[i] < 0) or stereo reprojection edge per keypoint that holds a map
+ * point, four rounds of at most ten Levenberg-Marquardt iterations with an
+ * inlier / outlier classification after each. The arithmetic restates what
+ * the reference makes g2o do, in double.
+ *
+ * Inputs, as the searches leave them: kps = mvKeysUn (x, y, octave are read),
+ * uright = mvuRight (NULL: a monocular frame, every edge monocular),
+ * assign[i] >= 0 = the row of keypoint i's map point in the table mps (the
+ * out / d_out convention of the pose searches), < 0 = no point; mps: pos is
+ * read, and obs_positive for n_inliers_with_obs; inv_sigma2 =
+ * mvInvLevelSigma2 (nlevels <= 16 floats, host); cam = fx, fy, cx, cy, mbf
+ * and the frame's mTcw on entry.
+ * Outputs: Tcw = rows 0..2 of the new mTcw (the old one, bit for bit, when
+ * the frame has fewer than 3 correspondences); pose = orbm_prepare_pose(
+ * ORBM_PROJ_KEYFRAME, ...) of the camera with the new Tcw, byte for byte;
+ * outlier[i] = mvbOutlier[i], written only where keypoint i has a
+ * correspondence; *result below. Tcw, pose, outlier and result may each be
+ * NULL. With ORBM_POSEOPT_DISCARD_OUTLIERS, assign[i] = -1 for every outlier
+ * (src/Tracking.cc:983-988).
+ * A keypoint whose octave is outside [0, nlevels) or whose row is outside
+ * [0, nmp) is treated as one without a point and sets status bit 256. */
+typedef struct orbm_poseopt_result {
+  int32_t ret;                /* the function's return value: n_initial - n_bad, 0 below 3 correspondences */
+  int32_t n_initial;          /* nInitialCorrespondences */
+  int32_t n_bad;              /* nBad of the last round that ran */
+  int32_t n_inliers_with_obs; /* inliers whose point has obs_positive: nmatchesMap (src/Tracking.cc:993),
+                                 mnMatchesInliers (:1033) */
+  int32_t rounds;             /* rounds run: 0 (below 3), 1 (below 10) or 4 */
+  int32_t trials;             /* Levenberg-Marquardt trials of all rounds */
+  int32_t rejected;           /* trials whose step was rejected */
+  int32_t reserved;
+} orbm_poseopt_result; /* 32 B */
+
+#define ORBM_POSEOPT_DISCARD_OUTLIERS 1
+
+/* Host only: runs without a device. Edges accumulate in keypoint order, as
+ * g2o's do. *status (may be NULL) gets 0 or bit 256. n is not bounded. */
+int orbm_pose_optimization_host(const orbx_kp* kps, int n, const float* uright, int* assign,
+                                const orbm_map_point_world* mps, int nmp, const float* inv_sigma2,
+                                int nlevels, const orbm_camera* cam, int flags, float* Tcw,
+                                orbm_pose* pose, uint8_t* outlier, orbm_poseopt_result* result,
+                                int* status);
+
+/* The same on the device from host arrays, synchronous, one round trip.
+ * n <= max_kps. Sums over the edges are reduced lane -> wave -> workgroup in a
+ * fixed order, so Tcw may differ from the host function's by double rounding
+ * (each float equal or adjacent); flags and counts are those of the same
+ * arithmetic. Status bit 256 is left for orbm_get_status. */
+int orbm_pose_optimization(orbm_handle m, const orbx_kp* kps, int n, const float* uright, int* assign,
+                           const orbm_map_point_world* mps, int nmp, const float* inv_sigma2,
+                           int nlevels, const orbm_camera* cam, int flags, float* Tcw,
+                           orbm_pose* pose, uint8_t* outlier, orbm_poseopt_result* result);
+
+/* Device-resident and asynchronous on `stream`, one workgroup per frame:
+ * frame f's keypoints at d_kps + f*kp_pitch (d_n[f] of them; d_uright,
+ * d_assign and d_outlier likewise at kp_pitch), its map points at d_mps +
+ * f*mp_pitch (d_nmp[f] rows), its camera d_cams[f]; d_Tcw + 12*f, d_pose[f],
+ * d_result[f]. Slots from d_n[f] on are not touched. Frames without
+ * correspondences are valid anywhere in the batch. kp_pitch <= max_kps; a
+ * frame's edges stay in LDS up to a pitch of 4096, above that in the handle's
+ * workspace. The output bits of a frame do not depend on the batch size, its
+ * slot or the run. */
+int orbm_pose_optimization_batch(orbm_handle m, const orbx_kp* d_kps, const int* d_n, int kp_pitch,
+                                 const float* d_uright, int* d_assign,
+                                 const orbm_map_point_world* d_mps, const int* d_nmp, int mp_pitch,
+                                 const float* inv_sigma2, int nlevels, const orbm_camera* d_cams,
+                                 int frames, int flags, float* d_Tcw, orbm_pose* d_pose,
+                                 uint8_t* d_outlier, orbm_poseopt_result* d_result, void* stream);
 
 /* DBoW2::FeatureVector as CSR: nodes[k] ascending NodeIds; the feature
  * indices of node k are idx[off[k] .. off[k+1]). Each feature index appears

@@ -236,6 +236,14 @@ def lib() -> C.CDLL:
         L.orbm_refresh_map_points.argtypes = ([C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_uint32,
                                                                    C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                                                    C.c_void_p, C.c_int, C.c_void_p, C.c_void_p])
+        # kps, n, uright, assign, mps, nmp, inv_sigma2, nlevels, cam, flags, Tcw, pose, outlier, result
+        PO = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+              C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.orbm_pose_optimization_host.argtypes = PO + [C.POINTER(C.c_int)]
+        L.orbm_pose_optimization.argtypes = [C.c_void_p] + PO
+        L.orbm_pose_optimization_batch.argtypes = (
+            [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                                                C.c_int] + [C.c_void_p] * 5)
         L.orbm_prepare_sim3_match.argtypes = [C.POINTER(OrbmCamera), C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
                                               C.c_void_p, C.POINTER(OrbmPose)]
         L.orbm_fuse.argtypes = (PS + [C.c_void_p, GridBounds, C.c_void_p, C.c_void_p, C.c_int, C.c_float,
@@ -339,6 +347,11 @@ ORBM_PROJ_LAST_FRAME, ORBM_PROJ_KEYFRAME, ORBM_PROJ_SIM3 = 1, 2, 3
 ORBM_PROJ_FUSE, ORBM_PROJ_FUSE_SIM3, ORBM_PROJ_SIM3_MATCH = 4, 5, 6
 
 # orbm_observation, orbm_keyframe_ref, orbm_point_refkf (include/orbx_c.h): 8, 16 and 8 bytes
+POSEOPT_RESULT_DTYPE = np.dtype([("ret", "<i4"), ("n_initial", "<i4"), ("n_bad", "<i4"),
+                                 ("n_inliers_with_obs", "<i4"), ("rounds", "<i4"), ("trials", "<i4"),
+                                 ("rejected", "<i4"), ("reserved", "<i4")])
+assert POSEOPT_RESULT_DTYPE.itemsize == 32
+POSEOPT_DISCARD_OUTLIERS = 1
 OBSERVATION_DTYPE = np.dtype([("kf", "<u4"), ("desc_row", "<u4")])
 KEYFRAME_REF_DTYPE = np.dtype([("Ow", "<f4", (3,)), ("bad", "<u4")])
 POINT_REFKF_DTYPE = np.dtype([("kf", "<u4"), ("octave", "<i4")])

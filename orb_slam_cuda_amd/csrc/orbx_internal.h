@@ -360,6 +360,30 @@ struct RefreshArgs {
 };
 size_t refresh_ws_bytes(int points);
 int launch_refresh_map_points(const RefreshArgs& A, void* stream);
+// orbx_poseopt.hip — Optimizer::PoseOptimization, one frame per workgroup (the
+// arithmetic and status bit 256 are in orbx_poseopt.cuh)
+constexpr int kPoLdsEdges = 4096;  // frame pitches up to this keep their edge records in LDS (32 bytes each)
+struct PoseOptArgs {
+  const orbx_kp* kps;
+  const int* n;
+  int kp_pitch;
+  const float* uright;  // or null
+  int* assign;
+  const orbm_map_point_world* mps;
+  const int* nmp;
+  int mp_pitch;
+  const float* inv_sigma2;  // host, nlevels
+  int nlevels;
+  const orbm_camera* cams;
+  int frames, flags;
+  float* Tcw;                   // or null
+  orbm_pose* pose;              // or null
+  uint8_t* outlier;             // or null
+  orbm_poseopt_result* result;  // or null
+  int* err;                     // the handle's status word
+};
+size_t poseopt_spill_bytes(int kp_pitch, int frames);  // workspace of a launch (0 up to kPoLdsEdges)
+int launch_pose_optimization(const PoseOptArgs& P, void* spill, void* stream);
 // orbx_triangulate.hip — SearchForTriangulation, one keyframe pair per workgroup
 struct TriSide {  // one side of the pairs; pitches of 0 share one keyframe across pairs
   const orbx_kp* kps;

@@ -3,7 +3,7 @@
 // host-array entry points staged through the handle's arena. The kernels are in
 // orbx_top2.hip, orbx_bow.hip, orbx_init.hip, orbx_stereo.hip,
 // orbx_project.hip, orbx_project_pose.hip, orbx_frustum.hip,
-// orbx_triangulate.hip and orbx_mappoint.hip.
+// orbx_triangulate.hip, orbx_mappoint.hip and orbx_poseopt.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -21,6 +21,7 @@
 #include "orbx_internal.h"
 #include "orbx_mappoint.cuh"
 #include "orbx_posemath.cuh"
+#include "orbx_poseopt.cuh"
 
 using namespace orbx;
 
@@ -63,9 +64,11 @@ struct orbx_matcher {
   size_t view_ws_bytes = 0;
   uint8_t* refresh_ws = nullptr;  // RefreshMapPoints: class counters and work lists
   size_t refresh_ws_bytes = 0;
+  uint8_t* po_ws = nullptr;  // PoseOptimization: edge records of frame pitches above kPoLdsEdges
+  size_t po_ws_bytes = 0;
   hipStream_t stream = nullptr;
-  WsOrder ws;  // stream order of cand / stereo_sad / pose_picks / view_ws / refresh_ws / bow_* across caller streams
-  // streams of the launches that may set `err` (top-2, SearchByBoW, SearchLocalPoints, RefreshMapPoints)
+  WsOrder ws;  // stream order of cand / stereo_sad / pose_picks / view_ws / refresh_ws / po_ws / bow_* across caller streams
+  // streams of the launches that may set `err` (top-2, SearchByBoW, SearchLocalPoints, RefreshMapPoints, PoseOptimization)
   StreamMarks errm;
   // staging for the synchronous entry points
   void* stage = nullptr;
@@ -242,6 +245,7 @@ int orbm_destroy(orbm_handle m) {
   if (m->pose_picks) (void)hipFree(m->pose_picks);
   if (m->view_ws) (void)hipFree(m->view_ws);
   if (m->refresh_ws) (void)hipFree(m->refresh_ws);
+  if (m->po_ws) (void)hipFree(m->po_ws);
   if (m->stage) (void)hipFree(m->stage);
   if (m->h_stage) (void)hipHostFree(m->h_stage);
   if (m->stream) (void)hipStreamDestroy(m->stream);
@@ -1137,6 +1141,185 @@ int orbm_refresh_map_points(orbm_handle m, const orbm_observation* obs, const ui
   return ORBX_OK;
 }
 
+// ------------------------------------------- Optimizer::PoseOptimization
+namespace {
+
+// the sums of po_run over host edges, edge after edge in keypoint order
+struct HostPoCtx {
+  std::vector<PoEdge>& E;
+  PoCam cam;
+  void linearise(const PoPose& est, bool robust, double* acc) {
+    for (int k = 0; k < kPoSums; ++k) acc[k] = 0.0;
+    for (const PoEdge& e : E)
+      if (!(e.tag & kPoOutlier)) po_edge_linearise(cam, est, e, robust, acc);
+  }
+  double robust_chi2(const PoPose& est, bool robust) {
+    double s = 0.0;
+    for (const PoEdge& e : E)
+      if (!(e.tag & kPoOutlier)) s += po_edge_robust_chi2(cam, est, e, robust);
+    return s;
+  }
+  int classify(const PoPose& est, const PoPose& err_pose) {
+    int bad = 0;
+    for (PoEdge& e : E) {
+      const bool out = po_is_outlier(e, po_edge_chi2(cam, (e.tag & kPoOutlier) ? est : err_pose, e));
+      e.tag = out ? (e.tag | kPoOutlier) : (e.tag & ~kPoOutlier);
+      bad += out ? 1 : 0;
+    }
+    return bad;
+  }
+};
+
+}  // namespace
+
+int orbm_pose_optimization_host(const orbx_kp* kps, int n, const float* uright, int* assign,
+                                const orbm_map_point_world* mps, int nmp, const float* inv_sigma2, int nlevels,
+                                const orbm_camera* cam, int flags, float* Tcw, orbm_pose* pose, uint8_t* outlier,
+                                orbm_poseopt_result* result, int* status) {
+  if (n < 0 || nmp < 0 || !cam || !inv_sigma2 || nlevels < 1 || nlevels > kMaxLevels || (n && (!kps || !assign)) ||
+      (nmp && !mps))
+    return mfail(ORBX_EINVAL, "bad argument");
+  // an edge's tag holds the keypoint index in 16 bits; the index travels beside it here
+  std::vector<PoEdge> E;
+  std::vector<int> index;
+  int st_bits = 0;
+  for (int i = 0; i < n; ++i) {
+    const int row = assign[i];
+    if (row < 0) continue;
+    const int octave = kps[i].octave;
+    if (row >= nmp || octave < 0 || octave >= nlevels) {
+      st_bits |= kStatusPoseOptSkipped;
+      continue;
+    }
+    const float u = uright ? uright[i] : -1.0f;
+    PoEdge e;
+    for (int k = 0; k < 3; ++k) e.X[k] = mps[row].pos[k];
+    e.obs[0] = kps[i].x;
+    e.obs[1] = kps[i].y;
+    e.obs[2] = u;
+    e.w = inv_sigma2[octave];
+    e.tag = (u < 0 ? 0u : kPoStereo) | (mps[row].obs_positive ? kPoObs : 0u);
+    E.push_back(e);
+    index.push_back(i);
+  }
+  const int ne = (int)E.size();
+  PoStats st{0, 0, 0, 0};
+  float Tout[12];
+  std::memcpy(Tout, cam->Tcw, sizeof Tout);
+  if (ne >= 3) {
+    HostPoCtx ctx{E, PoCam{(double)cam->fx, (double)cam->fy, (double)cam->cx, (double)cam->cy, (double)cam->mbf}};
+    PoPose T0, est;
+    po_from_Tcw(cam->Tcw, &T0);
+    po_run(ctx, T0, ne, &est, &st);
+    po_to_Tcw(est, Tout);
+  }
+  int with_obs = 0;
+  for (int k = 0; k < ne; ++k) {
+    const bool out = (E[k].tag & kPoOutlier) != 0;
+    if (outlier) outlier[index[k]] = out ? 1 : 0;
+    if (out && (flags & ORBM_POSEOPT_DISCARD_OUTLIERS)) assign[index[k]] = -1;
+    with_obs += (!out && (E[k].tag & kPoObs)) ? 1 : 0;
+  }
+  if (Tcw) std::memcpy(Tcw, Tout, sizeof Tout);
+  if (pose) pose_from_rt(*cam, Tout, pose);
+  if (result) {
+    result->ret = ne >= 3 ? ne - st.n_bad : 0;
+    result->n_initial = ne;
+    result->n_bad = st.n_bad;
+    result->n_inliers_with_obs = with_obs;
+    result->rounds = st.rounds;
+    result->trials = st.trials;
+    result->rejected = st.rejected;
+    result->reserved = 0;
+  }
+  if (status) *status = st_bits;
+  return ORBX_OK;
+}
+
+int orbm_pose_optimization_batch(orbm_handle m, const orbx_kp* d_kps, const int* d_n, int kp_pitch,
+                                 const float* d_uright, int* d_assign, const orbm_map_point_world* d_mps,
+                                 const int* d_nmp, int mp_pitch, const float* inv_sigma2, int nlevels,
+                                 const orbm_camera* d_cams, int frames, int flags, float* d_Tcw, orbm_pose* d_pose,
+                                 uint8_t* d_outlier, orbm_poseopt_result* d_result, void* stream) {
+  if (!m || !d_kps || !d_n || !d_assign || !d_mps || !d_nmp || !inv_sigma2 || !d_cams || frames < 1 || kp_pitch < 1 ||
+      mp_pitch < 1 || nlevels < 1 || nlevels > kMaxLevels)
+    return mfail(ORBX_EINVAL, "bad argument");
+  if (kp_pitch > m->max_kps) return mfail(ORBX_ECAPACITY, "kp_pitch %d above the handle's max_kps %d", kp_pitch, m->max_kps);
+  MHIP(hipSetDevice(m->device));
+  hipStream_t s = (hipStream_t)stream;
+  const size_t need = poseopt_spill_bytes(kp_pitch, frames);
+  if (need) {
+    if (m->ws.before(s)) return mfail(ORBX_EDEVICE, "stream wait on the workspace failed");
+    if (m->po_ws_bytes < need) {
+      if (m->ws.ev) MHIP(hipEventSynchronize(m->ws.ev));
+      if (m->po_ws) MHIP(hipFree(m->po_ws));
+      m->po_ws = nullptr;
+      m->po_ws_bytes = 0;
+      if (hipMalloc(&m->po_ws, need) != hipSuccess) return mfail(ORBX_ENOMEM, "pose optimisation workspace");
+      m->po_ws_bytes = need;
+    }
+  }
+  PoseOptArgs A{};
+  A.kps = d_kps;
+  A.n = d_n;
+  A.kp_pitch = kp_pitch;
+  A.uright = d_uright;
+  A.assign = d_assign;
+  A.mps = d_mps;
+  A.nmp = d_nmp;
+  A.mp_pitch = mp_pitch;
+  A.inv_sigma2 = inv_sigma2;
+  A.nlevels = nlevels;
+  A.cams = d_cams;
+  A.frames = frames;
+  A.flags = flags;
+  A.Tcw = d_Tcw;
+  A.pose = d_pose;
+  A.outlier = d_outlier;
+  A.result = d_result;
+  A.err = m->err;
+  if (launch_pose_optimization(A, need ? m->po_ws : nullptr, stream))
+    return mfail(ORBX_EDEVICE, "pose optimisation launch: %s", hipGetErrorString(hipGetLastError()));
+  if ((need && m->ws.after(s)) || m->errm.mark(s)) return mfail(ORBX_EDEVICE, "event record failed");
+  return ORBX_OK;
+}
+
+int orbm_pose_optimization(orbm_handle m, const orbx_kp* kps, int n, const float* uright, int* assign,
+                           const orbm_map_point_world* mps, int nmp, const float* inv_sigma2, int nlevels,
+                           const orbm_camera* cam, int flags, float* Tcw, orbm_pose* pose, uint8_t* outlier,
+                           orbm_poseopt_result* result) {
+  if (!m || n < 0 || nmp < 0 || !cam || (n && (!kps || !assign)) || (nmp && !mps))
+    return mfail(ORBX_EINVAL, "bad argument");
+  if (n > m->max_kps) return mfail(ORBX_ECAPACITY, "%d keypoints above the handle's max_kps %d", n, m->max_kps);
+  MHIP(hipSetDevice(m->device));
+  const size_t kp = std::max(n, 1), np = std::max(nmp, 1);
+  int rc;
+  Stage st(m);
+  auto dk = st.slot<orbx_kp>(kp);
+  auto dn = st.slot<int>(2);
+  auto du = st.slot<float>(kp);
+  auto da = st.slot<int>(kp);
+  auto dm = st.slot<orbm_map_point_world>(np);
+  auto dc = st.slot<orbm_camera>(1);
+  auto dT = st.slot<float>(12);
+  auto dp = st.slot<orbm_pose>(1);
+  auto dout = st.slot<uint8_t>(kp);
+  auto dr = st.slot<orbm_poseopt_result>(1);
+  const int counts[2] = {n, nmp};
+  // the caller's flags go up too: the bytes of keypoints without a point come back as they were
+  if ((rc = st.reserve()) || (rc = st.up(dk, kps, n)) || (rc = st.up(dn, counts, 2)) || (rc = st.up(du, uright, n)) ||
+      (rc = st.up(da, (const int*)assign, n)) || (rc = st.up(dm, mps, nmp)) || (rc = st.up(dc, cam, 1)) ||
+      (rc = st.up(dout, (const uint8_t*)outlier, n)) ||
+      (rc = orbm_pose_optimization_batch(m, dk, dn, (int)kp, uright ? (float*)du : nullptr, da, dm, (int*)dn + 1,
+                                         (int)np, inv_sigma2, nlevels, dc, 1, flags, dT, dp,
+                                         outlier ? (uint8_t*)dout : nullptr, dr, st.st)) ||
+      (Tcw && (rc = st.down(Tcw, dT, 12))) || (pose && (rc = st.down(pose, dp, 1))) ||
+      (outlier && (rc = st.down(outlier, dout, n))) || (result && (rc = st.down(result, dr, 1))) ||
+      ((flags & ORBM_POSEOPT_DISCARD_OUTLIERS) && (rc = st.down(assign, da, n))) || (rc = st.finish()))
+    return rc;
+  return ORBX_OK;
+}
+
 // ---------------------------------------------- pose-projection overloads
 namespace {
 
@@ -1145,14 +1328,6 @@ void host_rx_t(const float* T, const float* x, float* d) {
   for (int r = 0; r < 3; ++r) {
     const float t = T[4 * r] * x[0] + T[4 * r + 1] * x[1] + T[4 * r + 2] * x[2];
     d[r] = (float)((double)t * 1.0 + (double)T[4 * r + 3] * 1.0);
-  }
-}
-// -R.t()*t via the general gemm path (double accumulation)
-void host_neg_rt_t(const float* T, float* d) {
-  for (int r = 0; r < 3; ++r) {
-    double s = 0;
-    for (int k = 0; k < 3; ++k) s += (double)T[4 * k + r] * (double)T[4 * k + 3];
-    d[r] = (float)(s * -1.0);
   }
 }
 // MapPoint::PredictScale's int level as a predicate of the ratio
@@ -1168,12 +1343,7 @@ int orbm_prepare_pose(int mode, const orbm_camera* cam, const float* Tlw, int mo
   if (!cam || !out || mode < ORBM_PROJ_LAST_FRAME || mode > ORBM_PROJ_FUSE_SIM3 ||
       (mode == ORBM_PROJ_LAST_FRAME && !Tlw))
     return mfail(ORBX_EINVAL, "bad argument");
-  orbm_pose p{};
-  p.fx = cam->fx;
-  p.fy = cam->fy;
-  p.cx = cam->cx;
-  p.cy = cam->cy;
-  p.mbf = cam->mbf;
+  float Rt[12];
   if (mode == ORBM_PROJ_SIM3 || mode == ORBM_PROJ_FUSE_SIM3) {
     // scw = sqrt(sRcw.row(0).dot(sRcw.row(0))); Rcw = sRcw/scw; tcw = t/scw
     // (src/ORBmatcher.cc:298-303, 986-991): Mat::dot in double, Mat / s = convertTo(1/s)
@@ -1182,12 +1352,12 @@ int orbm_prepare_pose(int mode, const orbm_camera* cam, const float* Tlw, int mo
     const float scw = (float)std::sqrt(d);
     if (!(scw > 0)) return mfail(ORBX_EINVAL, "Scw has a zero scale");
     const float a = (float)(1.0 / (double)scw);
-    for (int k = 0; k < 12; ++k) p.Rt[k] = S[k] * a + 0.0f;
+    for (int k = 0; k < 12; ++k) Rt[k] = S[k] * a + 0.0f;
   } else {
-    for (int k = 0; k < 12; ++k) p.Rt[k] = cam->Tcw[k];
+    for (int k = 0; k < 12; ++k) Rt[k] = cam->Tcw[k];
   }
-  host_neg_rt_t(p.Rt, p.Ow);  // Ow = -Rcw.t()*tcw
-  p.level_mode = 0;
+  orbm_pose p;
+  pose_from_rt(*cam, Rt, &p);  // intrinsics, Rt, Ow = -Rcw.t()*tcw, level_mode 0
   if (mode == ORBM_PROJ_LAST_FRAME) {
     // twc = -Rcw.t()*tcw; tlc = Rlw*twc + tlw (src/ORBmatcher.cc:1338-1349)
     float tlc[3];
@@ -1226,7 +1396,7 @@ int orbm_prepare_sim3_match(const orbm_camera* cam1, const float* T1w, const flo
     p.mbf = cam1->mbf;
     std::memcpy(p.Rt, d == 0 ? T1w : T2w, sizeof p.Rt);
     std::memcpy(p.Rt2, d == 0 ? S21 : S12, sizeof p.Rt2);
-    host_neg_rt_t(p.Rt, p.Ow);
+    neg_rt_t(p.Rt, p.Ow);
     out[d] = p;
   }
   return ORBX_OK;

@@ -42,6 +42,32 @@ __host__ __device__ inline float pose_row(const float* T, int r, float x, float 
   return pm_d2f(pm_dadd((double)t, (double)T[4 * r + 3]));
 }
 
+// Ow = -Rcw.t()*tcw of a 3x4 T via the general gemm path (double accumulation,
+// alpha = -1): orbm_prepare_pose on the host, the pose solve's orbm_pose on the
+// device
+__host__ __device__ inline void neg_rt_t(const float* T, float* d) {
+  for (int r = 0; r < 3; ++r) {
+    double s = 0;
+    for (int k = 0; k < 3; ++k) s = pm_dadd(s, pm_dmul((double)T[4 * k + r], (double)T[4 * k + 3]));
+    d[r] = pm_d2f(pm_dmul(s, -1.0));
+  }
+}
+
+// The orbm_pose of a camera whose 3x4 transform is Rt, as orbm_prepare_pose
+// fills it for every mode before the last-frame overload's level_mode: the
+// pose solve writes the same record on the device for its new Tcw.
+__host__ __device__ inline void pose_from_rt(const orbm_camera& cam, const float* Rt, orbm_pose* p) {
+  for (int k = 0; k < 12; ++k) p->Rt[k] = Rt[k];
+  neg_rt_t(p->Rt, p->Ow);
+  p->fx = cam.fx;
+  p->fy = cam.fy;
+  p->cx = cam.cx;
+  p->cy = cam.cy;
+  p->mbf = cam.mbf;
+  p->level_mode = 0;
+  for (int k = 0; k < 12; ++k) p->Rt2[k] = 0.0f;
+}
+
 // cv::norm (NORM_L2) of 3 floats: sqrt of the double sum of squares
 __host__ __device__ inline float norm3(float a, float b, float c) {
   const double s = pm_dadd(pm_dadd(pm_dmul((double)a, (double)a), pm_dmul((double)b, (double)b)),

@@ -24,6 +24,10 @@ for MapPoint::ComputeDistinctiveDescriptors / UpdateNormalAndDepth (src/MapPoint
     best, median = ComputeDistinctiveDescriptors(desc_rows)                               # one point, host
     normal, min_d, max_d = UpdateNormalAndDepth(pos, Ow_list, Ow_ref, ref_scale, last_scale)
 
+for Optimizer::PoseOptimization (src/Optimizer.cc:334-543), the pose solve between the searches:
+
+    Tcw, outlier, result = m.PoseOptimization(kps, assign, mps, inv_sigma2, cam, uright)
+
 and for the Frame constructors' tail (src/Frame.cc:118-227, 403-463, 642-663):
 
     F = ExtractRGBD(extractor, imGray, imDepth, K, distCoef, mbf, DepthMapFactor)  # one device round trip
@@ -819,6 +823,44 @@ class ORBmatcher:
             self._h, ptr(obs), ptr(off), ptr(ids), points, ptr(kfs), len(kfs), ptr(desc), len(desc), ptr(rf), ptr(sc),
             0 if sc is None else len(sc), ptr(mps), ptr(mpdesc), n_mps, ptr(best), ptr(med)), matcher=True)
         return best[:points], med[:points]
+
+    def PoseOptimization(self, kps, assign, mps, inv_sigma2, cam, uright=None, *, discard_outliers=False,
+                         outlier=None, host=False):
+        """Optimizer::PoseOptimization (src/Optimizer.cc:334-543) in one device round trip
+        (orbm_pose_optimization), or on the host alone with host=True (orbm_pose_optimization_host).
+        kps: KP_DTYPE (mvKeysUn); assign: int32 per keypoint, the row of its map point in mps
+        (MAP_POINT_WORLD_DTYPE) or -1, updated in place with discard_outliers (outliers become -1);
+        inv_sigma2 = mvInvLevelSigma2; cam: _lib.camera(...) with the frame's mTcw; uright = mvuRight or None
+        (monocular). outlier: a uint8 array updated in place where a keypoint has a point (default: zeros).
+        Returns (Tcw (3, 4) float32, outlier, result) with result a POSEOPT_RESULT_DTYPE record; the
+        orbm_pose of the new camera stays in self.last_pose. Keypoints left out for an octave or row out
+        of range set bit 256 of status() (host=True: self.last_host_status)."""
+        kps = np.ascontiguousarray(kps, KP_DTYPE)
+        n = len(kps)
+        if not (isinstance(assign, np.ndarray) and assign.dtype == np.int32 and assign.flags.c_contiguous
+                and len(assign) == n):
+            raise _lib.OrbxError(_lib.ORBX_EINVAL, "assign must be a contiguous int32 array, one entry per keypoint")
+        mps = np.ascontiguousarray(mps, MAP_POINT_WORLD_DTYPE)
+        sig = np.ascontiguousarray(inv_sigma2, np.float32)
+        ur = None if uright is None else np.ascontiguousarray(uright, np.float32)
+        if outlier is None:
+            outlier = np.zeros(max(n, 1), np.uint8)
+        elif not (isinstance(outlier, np.ndarray) and outlier.dtype == np.uint8 and outlier.flags.c_contiguous):
+            raise _lib.OrbxError(_lib.ORBX_EINVAL, "outlier must be a contiguous uint8 array")
+        Tcw = np.zeros(12, np.float32)
+        pose = _lib.OrbmPose()
+        res = np.zeros(1, _lib.POSEOPT_RESULT_DTYPE)
+        args = (ptr(kps), n, ptr(ur), ptr(assign), ptr(mps), len(mps), ptr(sig), len(sig), C.addressof(cam),
+                _lib.POSEOPT_DISCARD_OUTLIERS if discard_outliers else 0, ptr(Tcw), C.addressof(pose), ptr(outlier),
+                ptr(res))
+        if host:
+            st = C.c_int(0)
+            check(lib().orbm_pose_optimization_host(*args, C.byref(st)), matcher=True)
+            self.last_host_status = st.value
+        else:
+            check(lib().orbm_pose_optimization(self._h, *args), matcher=True)
+        self.last_pose = pose
+        return Tcw.reshape(3, 4), outlier[:n], res[0]
 
     def SearchByBoW(self, A: KeyFrame, B, out: list | None = None) -> int:
         """KF-Frame (B is a Frame) or KF-KF (B is a KeyFrame). Fills `out` with matched

@@ -3,7 +3,7 @@
 // mvKeysUn, mDescriptors, mBowVec, mFeatVec, mpORBvocabulary, the camera
 // (static fx .. invfy, mb, mbf), stereo fields (mvKeysRight,
 // mDescriptorsRight, mvuRight, mvDepth), the pose mTcw, mvpMapPoints,
-// mvbOutlier, the scale tables and the static image bounds mnMinX..mnMaxY
+// mvbOutlier, SetPose, the scale tables and the static image bounds mnMinX..mnMaxY
 // (Frame.h:110-186). ComputeBoW is src/Frame.cc:394-401; ComputeStereoMatches
 // (:465-639), isInFrustum (:268-324), UndistortKeyPoints (:403-433),
 // ComputeImageBounds (:435-463) and ComputeStereoFromRGBD (:642-663) are the
@@ -145,6 +145,8 @@ class Frame {
   // it compiles as written; ORBmatcher::SearchLocalPoints does the loop and the
   // search that follows in one device call.
   bool isInFrustum(MapPoint* pMP, float viewingCosLimit);
+  // Set the camera pose (src/Frame.cc:254-258; the stand-in keeps no mRcw / mtcw / mOw to update)
+  void SetPose(cv::Mat Tcw) { mTcw = Tcw.clone(); }
 
   ORBVocabulary* mpORBvocabulary = nullptr;
   ORBextractor* mpORBextractorLeft = nullptr;

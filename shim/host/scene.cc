@@ -13,6 +13,7 @@
 //   op 8 SearchForTriangulation(pKF1, pKF2, F12, ...)      LocalMapping.cc:301
 //   op 9 SearchByBoW(pKF, F, vpMapPointMatches)            Tracking.cc:842, 1465
 //   op 10 Tracking::SearchLocalPoints' body                Tracking.cc:1229-1279
+//   op 11 Optimizer::PoseOptimization(&CurrentFrame)       Tracking.cc:975, 1020
 // --scene-latency: the same scene rebuilt per call, only the method call on
 // the host clock (median / p99 over the calls after the warm ones).
 // Scene file: records of [u32 name length][name][u32 dtype 0 u8 / 1 i32 /
@@ -33,6 +34,7 @@
 #include "KeyFrame.h"
 #include "MapPoint.h"
 #include "ORBmatcher.h"
+#include "Optimizer.h"
 
 using namespace ORB_SLAM2;
 
@@ -444,6 +446,23 @@ static void run_op(const Scene& s, std::vector<int>& res, double* ms) {
       search_local_points(s, false, res);
       search_local_points(s, true, res);
       toc();
+      break;
+    }
+    case 11: {  // -> [return value, mvbOutlier..., mTcw rows 0..2 as the bits of 12 floats]
+      auto F = frame(s, "A", pool);
+      set_nobs(s, pool);
+      tic();
+      const int n = Optimizer::PoseOptimization(F.get());
+      toc();
+      res.push_back(n);
+      for (int i = 0; i < F->N; ++i) res.push_back(F->mvbOutlier[i] ? 1 : 0);
+      for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 4; ++c) {
+          const float v = F->mTcw.at<float>(r, c);
+          int bits;
+          memcpy(&bits, &v, 4);
+          res.push_back(bits);
+        }
       break;
     }
     default:
