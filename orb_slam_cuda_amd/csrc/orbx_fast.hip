@@ -302,7 +302,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ORBX_FAST_WA
       for (int c = lane; c < rw; c += 64) roi[r * kRoiStride + ox + c] = rows[(long long)r * pitch + cg.c0 + c];
   }
   const int sw = bw + 1;
-  for (int i = lane; i < (sw * (bh + 2) + 1 + 3) >> 2; i += 64) ((LDSP uint32_t*)sc)[i] = 0;
+  {
+    // the score map cleared by 16-byte stores: take() starts it on a 16-byte
+    // boundary and rounds its (largest-cell) size up to 16, so this cell's
+    // size rounded up stays inside it; two stores per lane cover 2 KB, the
+    // tight strides' maps (<= 40 x 41 + 1 bytes), the wide stride loops on
+    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+    const int nclr = (sw * (bh + 2) + 1 + 15) & ~15;
+    for (int o = 16 * lane; o < nclr; o += 1024) *(LDSP u32x4*)(sc + o) = (u32x4){0u, 0u, 0u, 0u};
+  }
   __syncthreads();
   stamp(0);
 
@@ -421,16 +429,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ORBX_FAST_WA
     const int e = list[i];
     const LDSP uint8_t* q = sc + u24mul((e >> 8) + 1, sw) + (e & 255) + 1;
     const int s = q[0];
-    bool gi = s >= ti && s > 0, gm = s >= tm && s > 0;
-    const int nbv[8] = {q[-1], q[1], q[-sw - 1], q[-sw], q[-sw + 1], q[sw - 1], q[sw], q[sw + 1]};
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int x = nbv[j];
-      if (x >= ti && x >= s) gi = false;
-      if (x >= tm && x >= s) gm = false;
-    }
-    *ki = gi;
-    *km = gm;
+    // a pixel kept at threshold th has s >= th, so a neighbour x >= s is also
+    // >= th: "no neighbour with x >= th and x >= s" is "s above its largest
+    // neighbour" at either threshold, and one maximum serves both
+    const int m1 = max(max(q[-1], q[1]), q[-sw - 1]), m2 = max(max(q[-sw], q[-sw + 1]), q[sw - 1]);
+    const bool top = s > max(max(m1, m2), max(q[sw], q[sw + 1])) && s > 0;
+    *ki = top && s >= ti;
+    *km = top && s >= tm;
   };
   uint32_t* out = slots + (long long)f * P.slots_per_frame + cg.slot_off;
   auto emit = [&](int e, int pos) {  // the kept pixel's key, row-major position pos in the cell's slots
