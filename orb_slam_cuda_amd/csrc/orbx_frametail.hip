@@ -14,7 +14,9 @@
 // The host half (the four corners of Frame::ComputeImageBounds, :435-463, and
 // orbx_undistort_points) is the same undistort_point, orbx_undistort.cuh.
 #include <algorithm>
+#include <cmath>
 
+#include "orbx_hostutil.h"
 #include "orbx_undistort.cuh"
 
 namespace orbx {
@@ -91,4 +93,86 @@ void image_bounds_host(const orbx_calib& c, int w, int h, orbm_grid_bounds* out)
   }
 }
 
+size_t depth_elem_size(int depth_type) {
+  return depth_type == ORBX_DEPTH_U16 ? 2 : depth_type == ORBX_DEPTH_F32 ? 4 : 0;
+}
+
+FrameTailParams tail_params(const orbx_calib& c, int kp_pitch, int depth_type, size_t frame_pitch, size_t row_stride,
+                            int w, int hh, float factor, float mbf) {
+  FrameTailParams P{};
+  P.calib = c;
+  P.kp_pitch = kp_pitch;
+  P.depth_type = depth_type;
+  P.convert = fabsf(factor - 1.0f) > 1e-5f || depth_type != ORBX_DEPTH_F32;  // src/Tracking.cc:276
+  P.w = w;
+  P.h = hh;
+  P.factor = factor;
+  P.mbf = mbf;
+  P.depth_frame_pitch = frame_pitch;
+  P.depth_row_stride = row_stride;
+  return P;
+}
+
 }  // namespace orbx
+
+// ------------------------------------------- C ABI (the handle-free entry points)
+using namespace orbx;
+
+extern "C" {
+
+int orbx_undistort_points(const orbx_calib* calib, const float* xy, int n, float* xy_out) {
+  if (!calib || n < 0 || (n && (!xy || !xy_out))) return g_err.fail(ORBX_EINVAL, "orbx_undistort_points: bad argument");
+  undistort_points_host(*calib, xy, n, xy_out);
+  return ORBX_OK;
+}
+
+int orbx_image_bounds(const orbx_calib* calib, int w, int hh, orbm_grid_bounds* out) {
+  if (!calib || !out || w < 0 || hh < 0) return g_err.fail(ORBX_EINVAL, "orbx_image_bounds: bad argument");
+  image_bounds_host(*calib, w, hh, out);
+  return ORBX_OK;
+}
+
+int orbx_frame_tail_batch(const orbx_calib* calib, const orbx_kp* d_kps, const int* d_counts, int kp_pitch,
+                          int batch, const void* d_depth_img, int depth_type, size_t depth_frame_pitch,
+                          size_t depth_row_stride, int w, int hh, float depth_factor, float mbf,
+                          orbx_kp* d_kps_un, float* d_uRight, float* d_depth, void* stream) {
+  if (!calib) return g_err.fail(ORBX_EINVAL, "orbx_frame_tail_batch: null calib");
+  if (batch < 0 || kp_pitch < 0) return g_err.fail(ORBX_EINVAL, "orbx_frame_tail_batch: negative batch or kp_pitch");
+  if (batch == 0 || kp_pitch == 0) return ORBX_OK;
+  if (!d_kps || !d_counts || !d_kps_un) return g_err.fail(ORBX_EINVAL, "orbx_frame_tail_batch: null keypoint buffer");
+  if (d_depth_img) {
+    const size_t es = depth_elem_size(depth_type);
+    if (!es) return g_err.fail(ORBX_EINVAL, "orbx_frame_tail_batch: unknown depth_type %d", depth_type);
+    if (w < 0 || hh < 0 || depth_row_stride < (size_t)w * es)
+      return g_err.fail(ORBX_EINVAL, "orbx_frame_tail_batch: depth_row_stride %zu below %d elements of %zu bytes",
+                  depth_row_stride, w, es);
+    if (depth_row_stride % es || depth_frame_pitch % es || (uintptr_t)d_depth_img % es)
+      return g_err.fail(ORBX_EINVAL, "orbx_frame_tail_batch: depth image not aligned to its %zu-byte elements", es);
+    if (batch > 1 && depth_frame_pitch < depth_row_stride * (size_t)hh)
+      return g_err.fail(ORBX_EINVAL, "orbx_frame_tail_batch: depth_frame_pitch %zu below one frame", depth_frame_pitch);
+    if (!d_uRight || !d_depth) return g_err.fail(ORBX_EINVAL, "orbx_frame_tail_batch: null uRight / depth output");
+  }
+  const FrameTailParams P = tail_params(*calib, kp_pitch, depth_type, depth_frame_pitch, depth_row_stride, w, hh,
+                                        depth_factor, mbf);
+  if (launch_frame_tail(P, d_kps, d_counts, batch, d_depth_img, d_kps_un, d_uRight, d_depth, stream))
+    return g_err.fail(ORBX_EDEVICE, "frame tail launch failed: %s", hipGetErrorString(hipGetLastError()));
+  return ORBX_OK;
+}
+
+int orbx_undistort_keypoints(const orbx_calib* calib, const orbx_kp* kps, int n, orbx_kp* kps_un) {
+  if (!calib || n < 0 || (n && (!kps || !kps_un))) return g_err.fail(ORBX_EINVAL, "orbx_undistort_keypoints: bad argument");
+  if (n == 0) return ORBX_OK;
+  const size_t kb = (size_t)n * sizeof(orbx_kp);
+  DeviceBuf in, out;  // in: the count (16 bytes) + the keypoints
+  int rc;
+  if ((rc = device_alloc(in, 16 + kb)) || (rc = device_alloc(out, kb))) return rc;
+  HIP_OK(g_err, hipMemcpy(in.p, &n, sizeof n, hipMemcpyHostToDevice));
+  HIP_OK(g_err, hipMemcpy(in.as<uint8_t>() + 16, kps, kb, hipMemcpyHostToDevice));
+  if ((rc = orbx_frame_tail_batch(calib, (const orbx_kp*)(in.as<uint8_t>() + 16), in.as<int>(), n, 1, nullptr, 0, 0, 0,
+                                  0, 0, 1.f, 0.f, out.as<orbx_kp>(), nullptr, nullptr, nullptr)))
+    return rc;
+  HIP_OK(g_err, hipMemcpy(kps_un, out.p, kb, hipMemcpyDeviceToHost));  // the null stream: after the kernel
+  return ORBX_OK;
+}
+
+}  // extern "C"

@@ -59,7 +59,7 @@ struct LevelGeom {
 };
 
 // keypoint slots per orient+BRIEF workgroup; every level's slot range starts
-// at a multiple of it (orbx_host.hip plan)
+// at a multiple of it (orbx_plan.hip)
 constexpr int kKpGroup = 8;
 
 struct CellGeom {
@@ -101,7 +101,7 @@ struct ExtractParams {
                                // level 0's second entry: {int2 offset of the band's staged row entries, their count}
   int pyr_nct;                 // column tiles per band
   int pyr_ctiles;              // int2 offset: per (tile, level) {comp_lo, comp_hi}, {own_lo, own_hi}, {LDS pitch, LDS origin},
-                               // {int2 offset of the level's column records (orbx_host.hip plan_band_pyramid), 0}
+                               // {int2 offset of the level's column records (orbx_plan.hip plan_band_pyramid), 0}
   int pyr_lds_a, pyr_lds_b;    // LDS bytes of the even-level and odd-level row buffers
   int pyr_lds_y;               // LDS bytes of the band's staged row coefficients
   // alternative tilings, one picked per launch (launch_pyramid): the
@@ -225,6 +225,18 @@ int launch_extract(const ExtractParams& P, const ExtractBuffers& X, const uint8_
                    int batch, size_t frame_pitch, size_t row_stride, orbx_kp* d_kps,
                    uint8_t* d_desc, int* d_counts, void* stream, void** stage_events,
                    void* pyr_event = nullptr, int* status_dst = nullptr, const char* stage_order = nullptr);
+// What the plan and the extractor handle ask the stage kernels' files: LDS
+// bytes of a launch (host arithmetic on the plan), the kernels whose
+// dynamic-LDS limit the handle raises, and the band kernel's occupancy
+size_t quadtree_lds_bytes(const ExtractParams& P);  // orbx_quadtree.hip
+size_t quadtree_legacy_lds_bytes(const ExtractParams& P);
+size_t quadtree_sorted_lds_bytes(const ExtractParams& P, int big);
+int quadtree_sorted_ownmax(const ExtractParams& P, int big, size_t budget);
+const void* quadtree_kernel_ptr(const ExtractParams& P);
+size_t pyr_band_lds_bytes(const ExtractParams& P);  // orbx_pyramid.hip
+const void* pyr_band_kernel_ptr();
+int pyr_band_occupancy(size_t lds);
+void blur_strip_dims(int small, int* strip, int* rows);  // orbx_blur.hip
 
 // orbx_top2.hip — dense Hamming best/second search
 int launch_hamming_top2(const uint8_t* A, size_t a_pitch, const int* nA, int a_cap,
@@ -470,26 +482,26 @@ struct StreamMarks {
     n = 0;
   }
 };
-// orbx_host.hip: the workspace order of an extractor (its pyramid is read by
+// orbx_extractor.hip: the workspace order of an extractor (its pyramid is read by
 // the stereo matcher)
 WsOrder* extractor_ws(orbx_handle h);
-// orbx_host.hip: where the handle's last orbx_extract left its frame's
+// orbx_extractor.hip: where the handle's last orbx_extract left its frame's
 // outputs on the device (count, keypoints at a pitch of `cap`, descriptors);
 // an empty image leaves cap = 0 and null pointers (no keypoints);
 // ORBX_EINVAL when the last extraction was not an orbx_extract call
 int extractor_last_output(orbx_handle h, const int** d_count, const orbx_kp** d_kps, const uint8_t** d_desc,
                           int* cap);
-// orbx_host.hip: raise a kernel's dynamic-LDS limit on the current device to at
+// orbx_runtime.hip: raise a kernel's dynamic-LDS limit on the current device to at
 // least `bytes` (never lowers it; process-wide, thread-safe)
 int raise_lds_limit(const void* fn, size_t bytes);
-// orbx_host.hip: the pyramid of frames [frame0, frame0 + n) of an extractor's last extraction
+// orbx_extractor.hip: the pyramid of frames [frame0, frame0 + n) of an extractor's last extraction
 int extractor_pyramid(orbx_handle h, int frame0, int n, LevelPtrs* lp, int* w, int* hgt, float* scale,
                       float* inv_scale, int* L);
-// orbx_host.hip: `bytes` from device memory to pinned host memory by a copy
+// orbx_runtime.hip: `bytes` from device memory to pinned host memory by a copy
 // kernel on `stream` (a blit launch, as a graph's memcpy node runs, instead of
 // a copy-engine transfer and its start-up latency)
 int copy_to_host_async(void* host_dst, const void* dev_src, size_t bytes, hipStream_t stream);
-// orbx_host.hip: the stereo Frame's two extractions (src/Frame.cc:77-80) as two
+// orbx_extractor.hip: the stereo Frame's two extractions (src/Frame.cc:77-80) as two
 // orbx_extract calls make them, from one thread and with one wait: left staged
 // and launched on its handle's stream, right on its own (the two run
 // concurrently), then `between(right's stream)` enqueues the work that reads
@@ -514,6 +526,9 @@ struct FrameTailParams {
   float factor, mbf;
   size_t depth_frame_pitch, depth_row_stride;  // bytes
 };
+size_t depth_elem_size(int depth_type);  // bytes of an ORBX_DEPTH_* element, 0 for an unknown type
+FrameTailParams tail_params(const orbx_calib& c, int kp_pitch, int depth_type, size_t frame_pitch, size_t row_stride,
+                            int w, int h, float factor, float mbf);
 // frame f: counts[f] keypoints at kps + f*kp_pitch -> kps_un (+ uright, depth
 // when depth_img is not null); slots from counts[f] on are not written
 int launch_frame_tail(const FrameTailParams& P, const orbx_kp* kps, const int* counts, int batch,

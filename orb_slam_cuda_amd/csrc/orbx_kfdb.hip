@@ -36,13 +36,12 @@
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <set>
-#include <string>
 #include <vector>
 
+#include "orbx_hostutil.h"
 #include "orbx_internal.h"
 
 namespace orbx {
@@ -292,16 +291,7 @@ __global__ __launch_bounds__(kDbThreads) void kfdb_add_kernel(const uint32_t* __
 using namespace orbx;
 
 namespace {
-thread_local std::string g_dberr;
-int dbfail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  g_dberr = buf;
-  return code;
-}
+thread_local ErrorSlot g_dberr;  // the orbdb_ family's last error
 const char* const kScoringNames[6] = {"L1_NORM", "L2_NORM", "CHI_SQUARE", "KL", "BHATTACHARYYA", "DOT_PRODUCT"};
 
 // the walk shared by L1, L2, chi-square, Bhattacharyya and the dot product:
@@ -327,12 +317,6 @@ double walk_shared(const uint32_t* w1, const double* v1, int n1, const uint32_t*
 }
 }  // namespace
 
-#define DBHIP(expr)                                                                             \
-  do {                                                                                          \
-    hipError_t e_ = (expr);                                                                     \
-    if (e_ != hipSuccess) return dbfail(ORBX_EDEVICE, "%s: %s", #expr, hipGetErrorString(e_));  \
-  } while (0)
-
 struct orbdb_database {
   int device = 0, max_kf = 0, pitch = 0;
   // device storage
@@ -344,11 +328,9 @@ struct orbdb_database {
   double* q_values = nullptr;   // [kDbMaxWords]
   int* q_meta = nullptr;        // {n, max_common, n_exclude}
   orbdb_hit* hits = nullptr;    // [max_kf]
-  int* ilist = nullptr;         // exclude / slot lists (grows)
-  size_t ilist_cap = 0;
-  double* dout = nullptr;  // orbdb_score_slots results (grows)
-  size_t dout_cap = 0;
-  int* h_slots = nullptr;  // pinned: orbdb_add_batch's slot list [max_kf]
+  DeviceBuf ilist;              // exclude / slot lists, ints (grows)
+  DeviceBuf dout;               // orbdb_score_slots results, doubles (grows)
+  PinnedBuf h_slots;            // orbdb_add_batch's slot list [max_kf]
   hipStream_t stream = nullptr;
   WsOrder order;  // the storage's last user
   // host mirror
@@ -368,13 +350,7 @@ struct orbdb_database {
 };
 
 static int db_reserve_ilist(orbdb_database* db, size_t ints) {
-  if (db->ilist_cap >= ints) return ORBX_OK;
-  if (db->ilist) (void)hipFree(db->ilist);
-  db->ilist = nullptr;
-  db->ilist_cap = 0;
-  if (hipMalloc(&db->ilist, ints * 4) != hipSuccess) return dbfail(ORBX_ENOMEM, "list of %zu entries", ints);
-  db->ilist_cap = ints;
-  return ORBX_OK;
+  return db->ilist.reserve(ints * 4) == hipSuccess ? ORBX_OK : g_dberr.fail(ORBX_ENOMEM, "list of %zu entries", ints);
 }
 
 static int db_take_slot(orbdb_database* db) {
@@ -405,35 +381,35 @@ static int db_grid(int slots, int queries) {
 static int db_launch_query(orbdb_database* db, const uint32_t* d_qw, const double* d_qv, const int* d_qn, int pitch,
                            int queries, const int* d_excl, const int* d_nexcl, int excl_pitch, orbdb_hit* d_hits,
                            int* d_max, hipStream_t st) {
-  DBHIP(hipMemsetAsync(d_max, 0, (size_t)queries * 4, st));
+  HIP_OK(g_dberr, hipMemsetAsync(d_max, 0, (size_t)queries * 4, st));
   const dim3 grid(db_grid(db->max_kf, queries), queries);
   const size_t lds = q_lds_bytes(pitch);
   hipLaunchKernelGGL(kfdb_count_kernel, grid, dim3(kDbThreads), lds, st, db_dev(db), d_qw, d_qn, pitch, d_excl,
                      d_nexcl, excl_pitch, d_hits, d_max);
-  DBHIP(hipGetLastError());
+  HIP_OK(g_dberr, hipGetLastError());
   hipLaunchKernelGGL(kfdb_score_kernel, grid, dim3(kDbThreads), lds, st, db_dev(db), d_qw, d_qv, d_qn, pitch, d_hits,
                      d_max);
-  DBHIP(hipGetLastError());
+  HIP_OK(g_dberr, hipGetLastError());
   return ORBX_OK;
 }
 
 // the synchronous entry points' query upload: words, values, n into the staging
 static int db_stage_query(orbdb_database* db, const uint32_t* words, const double* values, int n, hipStream_t st) {
   if (n) {
-    DBHIP(hipMemcpyAsync(db->q_words, words, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    DBHIP(hipMemcpyAsync(db->q_values, values, (size_t)n * 8, hipMemcpyHostToDevice, st));
+    HIP_OK(g_dberr, hipMemcpyAsync(db->q_words, words, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    HIP_OK(g_dberr, hipMemcpyAsync(db->q_values, values, (size_t)n * 8, hipMemcpyHostToDevice, st));
   }
   return ORBX_OK;
 }
 
 extern "C" {
 
-const char* orbdb_last_error(void) { return g_dberr.c_str(); }
+const char* orbdb_last_error(void) { return g_dberr.msg.c_str(); }
 
 int orbv_score(int scoring, const uint32_t* w1, const double* v1, int n1, const uint32_t* w2, const double* v2,
                int n2, double* out) {
   if (!out || n1 < 0 || n2 < 0 || (n1 && (!w1 || !v1)) || (n2 && (!w2 || !v2)))
-    return dbfail(ORBX_EINVAL, "bad argument");
+    return g_dberr.fail(ORBX_EINVAL, "bad argument");
   double score = 0;
   switch (scoring) {
     case 0:  // L1Scoring (ScoringObject.cpp:23-68)
@@ -481,7 +457,7 @@ int orbv_score(int scoring, const uint32_t* w1, const double* v1, int n1, const 
       score = walk_shared(w1, v1, n1, w2, v2, n2, [](double& s, double vi, double wi) { s += vi * wi; });
       break;
     default:
-      return dbfail(ORBX_EINVAL, "unknown scoring %d", scoring);
+      return g_dberr.fail(ORBX_EINVAL, "unknown scoring %d", scoring);
   }
   *out = score;
   return ORBX_OK;
@@ -493,9 +469,11 @@ int orbdb_destroy(orbdb_handle db) {
   if (db->order.used) (void)hipEventSynchronize(db->order.ev);
   if (db->stream) (void)hipStreamSynchronize(db->stream);
   for (void* p : {(void*)db->words, (void*)db->values, (void*)db->n, (void*)db->q_words, (void*)db->q_values,
-                  (void*)db->q_meta, (void*)db->hits, (void*)db->ilist, (void*)db->dout})
+                  (void*)db->q_meta, (void*)db->hits})
     if (p) (void)hipFree(p);
-  if (db->h_slots) (void)hipHostFree(db->h_slots);
+  db->ilist.release();
+  db->dout.release();
+  db->h_slots.release();
   db->order.release();
   if (db->stream) (void)hipStreamDestroy(db->stream);
   delete db;
@@ -503,16 +481,16 @@ int orbdb_destroy(orbdb_handle db) {
 }
 
 int orbdb_create(int device, int max_keyframes, int word_pitch, int scoring, orbdb_handle* out) {
-  if (!out || max_keyframes < 1) return dbfail(ORBX_EINVAL, "bad argument");
+  if (!out || max_keyframes < 1) return g_dberr.fail(ORBX_EINVAL, "bad argument");
   if (scoring != 0) {
     if (scoring >= 1 && scoring <= 5)
-      return dbfail(ORBX_EINVAL, "scoring %s (%d) is not supported on the device: only L1_NORM (0)",
+      return g_dberr.fail(ORBX_EINVAL, "scoring %s (%d) is not supported on the device: only L1_NORM (0)",
                     kScoringNames[scoring], scoring);
-    return dbfail(ORBX_EINVAL, "unknown scoring %d", scoring);
+    return g_dberr.fail(ORBX_EINVAL, "unknown scoring %d", scoring);
   }
   if (word_pitch < 1 || word_pitch > kDbMaxWords)
-    return dbfail(ORBX_EINVAL, "word_pitch %d outside 1..%d", word_pitch, kDbMaxWords);
-  if (hipSetDevice(device) != hipSuccess) return dbfail(ORBX_EDEVICE, "no device %d", device);
+    return g_dberr.fail(ORBX_EINVAL, "word_pitch %d outside 1..%d", word_pitch, kDbMaxWords);
+  if (hipSetDevice(device) != hipSuccess) return g_dberr.fail(ORBX_EDEVICE, "no device %d", device);
   orbdb_database* db = new orbdb_database();
   db->device = device;
   db->max_kf = max_keyframes;
@@ -523,16 +501,16 @@ int orbdb_create(int device, int max_keyframes, int word_pitch, int scoring, orb
       hipMalloc(&db->q_words, (size_t)kDbMaxWords * 4) != hipSuccess ||
       hipMalloc(&db->q_values, (size_t)kDbMaxWords * 8) != hipSuccess || hipMalloc(&db->q_meta, 16) != hipSuccess ||
       hipMalloc(&db->hits, (size_t)max_keyframes * sizeof(orbdb_hit)) != hipSuccess ||
-      hipHostMalloc(&db->h_slots, (size_t)max_keyframes * 4) != hipSuccess) {
+      db->h_slots.alloc((size_t)max_keyframes * 4) != hipSuccess) {
     (void)hipGetLastError();
     orbdb_destroy(db);
-    return dbfail(ORBX_ENOMEM, "database allocation failed (%d keyframes x %d words)", max_keyframes, word_pitch);
+    return g_dberr.fail(ORBX_ENOMEM, "database allocation failed (%d keyframes x %d words)", max_keyframes, word_pitch);
   }
   if (hipStreamCreateWithFlags(&db->stream, hipStreamNonBlocking) != hipSuccess ||
       hipMemsetAsync(db->n, 0, (size_t)max_keyframes * 4, db->stream) != hipSuccess ||
       hipStreamSynchronize(db->stream) != hipSuccess) {
     orbdb_destroy(db);
-    return dbfail(ORBX_EDEVICE, "database set-up failed");
+    return g_dberr.fail(ORBX_EDEVICE, "database set-up failed");
   }
   db->live.assign(max_keyframes, 0);
   db->seq.assign(max_keyframes, 0);
@@ -546,19 +524,19 @@ int orbdb_create(int device, int max_keyframes, int word_pitch, int scoring, orb
 }
 
 int orbdb_size(orbdb_handle db, int* live, int* slots_high_water) {
-  if (!db) return dbfail(ORBX_EINVAL, "null handle");
+  if (!db) return g_dberr.fail(ORBX_EINVAL, "null handle");
   if (live) *live = db->nlive;
   if (slots_high_water) *slots_high_water = db->high_water;
   return ORBX_OK;
 }
 
 int orbdb_clear(orbdb_handle db) {
-  if (!db) return dbfail(ORBX_EINVAL, "null handle");
-  DBHIP(hipSetDevice(db->device));
+  if (!db) return g_dberr.fail(ORBX_EINVAL, "null handle");
+  HIP_OK(g_dberr, hipSetDevice(db->device));
   hipStream_t st = db->stream;
-  if (db->order.before_pending(st)) return dbfail(ORBX_EDEVICE, "stream order");
-  DBHIP(hipMemsetAsync(db->n, 0, (size_t)db->max_kf * 4, st));
-  DBHIP(hipStreamSynchronize(st));
+  if (db->order.before_pending(st)) return g_dberr.fail(ORBX_EDEVICE, "stream order");
+  HIP_OK(g_dberr, hipMemsetAsync(db->n, 0, (size_t)db->max_kf * 4, st));
+  HIP_OK(g_dberr, hipStreamSynchronize(st));
   std::fill(db->live.begin(), db->live.end(), 0);
   db->freed.clear();
   db->high_water = db->nlive = 0;
@@ -571,22 +549,22 @@ int orbdb_clear(orbdb_handle db) {
 }
 
 int orbdb_add(orbdb_handle db, const uint32_t* words, const double* values, int n, int* slot) {
-  if (!db || !slot || n < 0 || (n && (!words || !values))) return dbfail(ORBX_EINVAL, "bad argument");
-  if (n > db->pitch) return dbfail(ORBX_ECAPACITY, "BowVector of %d words > word_pitch %d", n, db->pitch);
-  if (db->nlive >= db->max_kf) return dbfail(ORBX_ECAPACITY, "database full (%d keyframes)", db->max_kf);
-  if (db->next_seq == UINT32_MAX) return dbfail(ORBX_ECAPACITY, "add sequence counter exhausted");
+  if (!db || !slot || n < 0 || (n && (!words || !values))) return g_dberr.fail(ORBX_EINVAL, "bad argument");
+  if (n > db->pitch) return g_dberr.fail(ORBX_ECAPACITY, "BowVector of %d words > word_pitch %d", n, db->pitch);
+  if (db->nlive >= db->max_kf) return g_dberr.fail(ORBX_ECAPACITY, "database full (%d keyframes)", db->max_kf);
+  if (db->next_seq == UINT32_MAX) return g_dberr.fail(ORBX_ECAPACITY, "add sequence counter exhausted");
   for (int i = 1; i < n; ++i)
-    if (words[i] <= words[i - 1]) return dbfail(ORBX_EINVAL, "words not ascending at %d", i);
-  DBHIP(hipSetDevice(db->device));
+    if (words[i] <= words[i - 1]) return g_dberr.fail(ORBX_EINVAL, "words not ascending at %d", i);
+  HIP_OK(g_dberr, hipSetDevice(db->device));
   hipStream_t st = db->stream;
-  if (db->order.before_pending(st)) return dbfail(ORBX_EDEVICE, "stream order");
+  if (db->order.before_pending(st)) return g_dberr.fail(ORBX_EDEVICE, "stream order");
   const int s = db->freed.empty() ? db->high_water : *db->freed.begin();
   if (n) {
-    DBHIP(hipMemcpyAsync(db->words + (size_t)s * db->pitch, words, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    DBHIP(hipMemcpyAsync(db->values + (size_t)s * db->pitch, values, (size_t)n * 8, hipMemcpyHostToDevice, st));
+    HIP_OK(g_dberr, hipMemcpyAsync(db->words + (size_t)s * db->pitch, words, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    HIP_OK(g_dberr, hipMemcpyAsync(db->values + (size_t)s * db->pitch, values, (size_t)n * 8, hipMemcpyHostToDevice, st));
   }
-  DBHIP(hipMemcpyAsync(db->n + s, &n, 4, hipMemcpyHostToDevice, st));
-  DBHIP(hipStreamSynchronize(st));
+  HIP_OK(g_dberr, hipMemcpyAsync(db->n + s, &n, 4, hipMemcpyHostToDevice, st));
+  HIP_OK(g_dberr, hipStreamSynchronize(st));
   *slot = db_take_slot(db);
   return ORBX_OK;
 }
@@ -594,42 +572,42 @@ int orbdb_add(orbdb_handle db, const uint32_t* words, const double* values, int 
 int orbdb_add_batch(orbdb_handle db, const uint32_t* d_bow_words, const double* d_bow_values, const int* d_bow_n,
                     int pitch, int frames, int* slots, void* stream) {
   if (!db || !d_bow_words || !d_bow_values || !d_bow_n || !slots || pitch < 1 || frames < 1)
-    return dbfail(ORBX_EINVAL, "bad argument");
+    return g_dberr.fail(ORBX_EINVAL, "bad argument");
   if (frames > db->max_kf - db->nlive)
-    return dbfail(ORBX_ECAPACITY, "database full (%d live + %d > %d keyframes)", db->nlive, frames, db->max_kf);
+    return g_dberr.fail(ORBX_ECAPACITY, "database full (%d live + %d > %d keyframes)", db->nlive, frames, db->max_kf);
   if ((uint64_t)db->next_seq + (uint64_t)frames >= UINT32_MAX)
-    return dbfail(ORBX_ECAPACITY, "add sequence counter exhausted");
-  DBHIP(hipSetDevice(db->device));
+    return g_dberr.fail(ORBX_ECAPACITY, "add sequence counter exhausted");
+  HIP_OK(g_dberr, hipSetDevice(db->device));
   hipStream_t st = (hipStream_t)stream;
   // after this wait the storage's previous user, and the pinned slot list's, has finished
-  if (db->order.before(st)) return dbfail(ORBX_EDEVICE, "stream order");
+  if (db->order.before(st)) return g_dberr.fail(ORBX_EDEVICE, "stream order");
   std::vector<int> hn(frames);
-  DBHIP(hipMemcpyAsync(hn.data(), d_bow_n, (size_t)frames * 4, hipMemcpyDeviceToHost, st));
-  DBHIP(hipStreamSynchronize(st));
+  HIP_OK(g_dberr, hipMemcpyAsync(hn.data(), d_bow_n, (size_t)frames * 4, hipMemcpyDeviceToHost, st));
+  HIP_OK(g_dberr, hipStreamSynchronize(st));
   for (int f = 0; f < frames; ++f) {
-    if (hn[f] < 0) return dbfail(ORBX_EINVAL, "frame %d: count %d", f, hn[f]);
+    if (hn[f] < 0) return g_dberr.fail(ORBX_EINVAL, "frame %d: count %d", f, hn[f]);
     if (hn[f] > db->pitch || hn[f] > pitch)
-      return dbfail(ORBX_ECAPACITY, "frame %d: BowVector of %d words > word_pitch %d", f, hn[f],
+      return g_dberr.fail(ORBX_ECAPACITY, "frame %d: BowVector of %d words > word_pitch %d", f, hn[f],
                     std::min(db->pitch, pitch));
   }
   if (db_reserve_ilist(db, (size_t)db->max_kf)) return ORBX_ENOMEM;
-  for (int f = 0; f < frames; ++f) slots[f] = db->h_slots[f] = db_take_slot(db);
-  DBHIP(hipMemcpyAsync(db->ilist, db->h_slots, (size_t)frames * 4, hipMemcpyHostToDevice, st));
+  for (int f = 0; f < frames; ++f) slots[f] = db->h_slots.as<int>()[f] = db_take_slot(db);
+  HIP_OK(g_dberr, hipMemcpyAsync(db->ilist.p, db->h_slots.p, (size_t)frames * 4, hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(kfdb_add_kernel, dim3(frames), dim3(kDbThreads), 0, st, d_bow_words, d_bow_values, d_bow_n, pitch,
-                     db->ilist, db->max_kf, db->words, db->values, db->n, db->pitch);
-  DBHIP(hipGetLastError());
-  if (db->order.after(st)) return dbfail(ORBX_EDEVICE, "stream order");
+                     db->ilist.as<int>(), db->max_kf, db->words, db->values, db->n, db->pitch);
+  HIP_OK(g_dberr, hipGetLastError());
+  if (db->order.after(st)) return g_dberr.fail(ORBX_EDEVICE, "stream order");
   return ORBX_OK;
 }
 
 int orbdb_erase(orbdb_handle db, int slot) {
-  if (!db) return dbfail(ORBX_EINVAL, "null handle");
-  if (slot < 0 || slot >= db->max_kf || !db->live[slot]) return dbfail(ORBX_EINVAL, "slot %d is not live", slot);
-  DBHIP(hipSetDevice(db->device));
+  if (!db) return g_dberr.fail(ORBX_EINVAL, "null handle");
+  if (slot < 0 || slot >= db->max_kf || !db->live[slot]) return g_dberr.fail(ORBX_EINVAL, "slot %d is not live", slot);
+  HIP_OK(g_dberr, hipSetDevice(db->device));
   hipStream_t st = db->stream;
-  if (db->order.before_pending(st)) return dbfail(ORBX_EDEVICE, "stream order");
-  DBHIP(hipMemsetAsync(db->n + slot, 0, 4, st));
-  DBHIP(hipStreamSynchronize(st));
+  if (db->order.before_pending(st)) return g_dberr.fail(ORBX_EDEVICE, "stream order");
+  HIP_OK(g_dberr, hipMemsetAsync(db->n + slot, 0, 4, st));
+  HIP_OK(g_dberr, hipStreamSynchronize(st));
   db->live[slot] = 0;
   db->freed.insert(slot);
   --db->nlive;
@@ -641,48 +619,42 @@ int orbdb_query_batch(orbdb_handle db, const uint32_t* d_bow_words, const double
                       int pitch, int queries, const int* d_exclude, const int* d_n_exclude, int exclude_pitch,
                       orbdb_hit* d_hits, int* d_max_common, void* stream) {
   if (!db || !d_bow_words || !d_bow_values || !d_bow_n || !d_hits || !d_max_common || queries < 1 || pitch < 1)
-    return dbfail(ORBX_EINVAL, "bad argument");
-  if (pitch > kDbMaxWords) return dbfail(ORBX_ECAPACITY, "pitch %d > %d words per query", pitch, kDbMaxWords);
-  if (queries > 65535) return dbfail(ORBX_ECAPACITY, "more than 65535 queries per call");
-  if (d_exclude && (!d_n_exclude || exclude_pitch < 1)) return dbfail(ORBX_EINVAL, "exclude list without counts");
-  DBHIP(hipSetDevice(db->device));
+    return g_dberr.fail(ORBX_EINVAL, "bad argument");
+  if (pitch > kDbMaxWords) return g_dberr.fail(ORBX_ECAPACITY, "pitch %d > %d words per query", pitch, kDbMaxWords);
+  if (queries > 65535) return g_dberr.fail(ORBX_ECAPACITY, "more than 65535 queries per call");
+  if (d_exclude && (!d_n_exclude || exclude_pitch < 1)) return g_dberr.fail(ORBX_EINVAL, "exclude list without counts");
+  HIP_OK(g_dberr, hipSetDevice(db->device));
   hipStream_t st = (hipStream_t)stream;
-  if (db->order.before(st)) return dbfail(ORBX_EDEVICE, "stream order");
+  if (db->order.before(st)) return g_dberr.fail(ORBX_EDEVICE, "stream order");
   const int rc = db_launch_query(db, d_bow_words, d_bow_values, d_bow_n, pitch, queries, d_exclude, d_n_exclude,
                                  exclude_pitch, d_hits, d_max_common, st);
   if (rc) return rc;
-  if (db->order.after(st)) return dbfail(ORBX_EDEVICE, "stream order");
+  if (db->order.after(st)) return g_dberr.fail(ORBX_EDEVICE, "stream order");
   return ORBX_OK;
 }
 
 int orbdb_score_slots(orbdb_handle db, const uint32_t* words, const double* values, int n, const int* slots,
                       int nslots, double* out) {
   if (!db || n < 0 || nslots < 0 || (n && (!words || !values)) || (nslots && (!slots || !out)))
-    return dbfail(ORBX_EINVAL, "bad argument");
-  if (n > kDbMaxWords) return dbfail(ORBX_ECAPACITY, "query of %d words > %d", n, kDbMaxWords);
+    return g_dberr.fail(ORBX_EINVAL, "bad argument");
+  if (n > kDbMaxWords) return g_dberr.fail(ORBX_ECAPACITY, "query of %d words > %d", n, kDbMaxWords);
   for (int k = 0; k < nslots; ++k)
     if (slots[k] < 0 || slots[k] >= db->max_kf || !db->live[slots[k]])
-      return dbfail(ORBX_EINVAL, "slot %d is not live", slots[k]);
+      return g_dberr.fail(ORBX_EINVAL, "slot %d is not live", slots[k]);
   if (!nslots) return ORBX_OK;
-  DBHIP(hipSetDevice(db->device));
+  HIP_OK(g_dberr, hipSetDevice(db->device));
   hipStream_t st = db->stream;
-  if (db->order.before_pending(st)) return dbfail(ORBX_EDEVICE, "stream order");
+  if (db->order.before_pending(st)) return g_dberr.fail(ORBX_EDEVICE, "stream order");
   int rc;
   if ((rc = db_reserve_ilist(db, (size_t)nslots))) return rc;
-  if (db->dout_cap < (size_t)nslots) {
-    if (db->dout) (void)hipFree(db->dout);
-    db->dout = nullptr;
-    db->dout_cap = 0;
-    if (hipMalloc(&db->dout, (size_t)nslots * 8) != hipSuccess) return dbfail(ORBX_ENOMEM, "%d scores", nslots);
-    db->dout_cap = (size_t)nslots;
-  }
+  if (db->dout.reserve((size_t)nslots * 8) != hipSuccess) return g_dberr.fail(ORBX_ENOMEM, "%d scores", nslots);
   if ((rc = db_stage_query(db, words, values, n, st))) return rc;
-  DBHIP(hipMemcpyAsync(db->ilist, slots, (size_t)nslots * 4, hipMemcpyHostToDevice, st));
+  HIP_OK(g_dberr, hipMemcpyAsync(db->ilist.p, slots, (size_t)nslots * 4, hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(kfdb_score_slots_kernel, dim3(db_grid(nslots, 1)), dim3(kDbThreads), q_lds_bytes(std::max(n, 1)),
-                     st, db_dev(db), db->q_words, db->q_values, n, db->ilist, nslots, db->dout);
-  DBHIP(hipGetLastError());
-  DBHIP(hipMemcpyAsync(out, db->dout, (size_t)nslots * 8, hipMemcpyDeviceToHost, st));
-  DBHIP(hipStreamSynchronize(st));
+                     st, db_dev(db), db->q_words, db->q_values, n, db->ilist.as<int>(), nslots, db->dout.as<double>());
+  HIP_OK(g_dberr, hipGetLastError());
+  HIP_OK(g_dberr, hipMemcpyAsync(out, db->dout.p, (size_t)nslots * 8, hipMemcpyDeviceToHost, st));
+  HIP_OK(g_dberr, hipStreamSynchronize(st));
   return ORBX_OK;
 }
 
@@ -691,28 +663,28 @@ int orbdb_query(orbdb_handle db, int mode, const uint32_t* words, const double* 
                 int* min_common) {
   if (!db || (mode != ORBDB_LOOP && mode != ORBDB_RELOC) || n < 0 || (n && (!words || !values)) || n_exclude < 0 ||
       (n_exclude && !exclude) || cap < 0 || (cap && (!cand_slots || !cand_scores)) || !ncand)
-    return dbfail(ORBX_EINVAL, "bad argument");
-  if (n > kDbMaxWords) return dbfail(ORBX_ECAPACITY, "query of %d words > %d", n, kDbMaxWords);
-  DBHIP(hipSetDevice(db->device));
+    return g_dberr.fail(ORBX_EINVAL, "bad argument");
+  if (n > kDbMaxWords) return g_dberr.fail(ORBX_ECAPACITY, "query of %d words > %d", n, kDbMaxWords);
+  HIP_OK(g_dberr, hipSetDevice(db->device));
   hipStream_t st = db->stream;
-  if (db->order.before_pending(st)) return dbfail(ORBX_EDEVICE, "stream order");
+  if (db->order.before_pending(st)) return g_dberr.fail(ORBX_EDEVICE, "stream order");
   int rc;
   if (n_exclude && (rc = db_reserve_ilist(db, (size_t)n_exclude))) return rc;
   if ((rc = db_stage_query(db, words, values, n, st))) return rc;
   const int meta[3] = {n, 0, n_exclude};
-  DBHIP(hipMemcpyAsync(db->q_meta, meta, sizeof meta, hipMemcpyHostToDevice, st));
-  if (n_exclude) DBHIP(hipMemcpyAsync(db->ilist, exclude, (size_t)n_exclude * 4, hipMemcpyHostToDevice, st));
+  HIP_OK(g_dberr, hipMemcpyAsync(db->q_meta, meta, sizeof meta, hipMemcpyHostToDevice, st));
+  if (n_exclude) HIP_OK(g_dberr, hipMemcpyAsync(db->ilist.p, exclude, (size_t)n_exclude * 4, hipMemcpyHostToDevice, st));
   const int hw = db->high_water;
   int maxc = 0;
   if (hw > 0) {
     if ((rc = db_launch_query(db, db->q_words, db->q_values, db->q_meta, std::max(n, 1), 1,
-                              n_exclude ? db->ilist : nullptr, n_exclude ? db->q_meta + 2 : nullptr,
+                              n_exclude ? db->ilist.as<int>() : nullptr, n_exclude ? db->q_meta + 2 : nullptr,
                               std::max(n_exclude, 1), db->hits, db->q_meta + 1, st)))
       return rc;
-    DBHIP(hipMemcpyAsync(db->h_hits.data(), db->hits, (size_t)hw * sizeof(orbdb_hit), hipMemcpyDeviceToHost, st));
-    DBHIP(hipMemcpyAsync(&maxc, db->q_meta + 1, 4, hipMemcpyDeviceToHost, st));
+    HIP_OK(g_dberr, hipMemcpyAsync(db->h_hits.data(), db->hits, (size_t)hw * sizeof(orbdb_hit), hipMemcpyDeviceToHost, st));
+    HIP_OK(g_dberr, hipMemcpyAsync(&maxc, db->q_meta + 1, 4, hipMemcpyDeviceToHost, st));
   }
-  DBHIP(hipStreamSynchronize(st));
+  HIP_OK(g_dberr, hipStreamSynchronize(st));
   // everything below is the host's: lKFsSharingWords in the reference's order
   // (first encounter walking the query's words upwards, each word's list in
   // insertion order), minCommonWords, lScoreAndMatch
@@ -749,7 +721,7 @@ int orbdb_query(orbdb_handle db, int mode, const uint32_t* words, const double* 
   }
   *ncand = cnt;
   if (min_common) *min_common = minc;
-  if (cnt > cap) return dbfail(ORBX_ECAPACITY, "%d candidates > cap %d", cnt, cap);
+  if (cnt > cap) return g_dberr.fail(ORBX_ECAPACITY, "%d candidates > cap %d", cnt, cap);
   return ORBX_OK;
 }
 
@@ -757,13 +729,13 @@ int orbdb_select_candidates(orbdb_handle db, int mode, const int* cand_slots, co
                             const int* neigh, float min_score, int* out_slots, int* nout) {
   if (!db || (mode != ORBDB_LOOP && mode != ORBDB_RELOC) || ncand < 0 || !nout ||
       (ncand && (!cand_slots || !cand_scores || !neigh || !out_slots)))
-    return dbfail(ORBX_EINVAL, "bad argument");
-  if (!db->queried[mode]) return dbfail(ORBX_EINVAL, "no orbdb_query of mode %d on this handle yet", mode);
+    return g_dberr.fail(ORBX_EINVAL, "bad argument");
+  if (!db->queried[mode]) return g_dberr.fail(ORBX_EINVAL, "no orbdb_query of mode %d on this handle yet", mode);
   for (int i = 0; i < ncand; ++i) {
-    if (cand_slots[i] < 0 || cand_slots[i] >= db->max_kf) return dbfail(ORBX_EINVAL, "candidate slot %d", cand_slots[i]);
+    if (cand_slots[i] < 0 || cand_slots[i] >= db->max_kf) return g_dberr.fail(ORBX_EINVAL, "candidate slot %d", cand_slots[i]);
     for (int k = 0; k < 10; ++k)
       if (neigh[i * 10 + k] < -1 || neigh[i * 10 + k] >= db->max_kf)
-        return dbfail(ORBX_EINVAL, "neighbour slot %d", neigh[i * 10 + k]);
+        return g_dberr.fail(ORBX_EINVAL, "neighbour slot %d", neigh[i * 10 + k]);
   }
   const std::vector<int>& common = db->common[mode];
   const int minc = db->min_common[mode];

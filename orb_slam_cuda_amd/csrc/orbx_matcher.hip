@@ -10,14 +10,13 @@
 #include <chrono>
 #include <climits>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
-#include <string>
 #include <vector>
 
+#include "orbx_hostutil.h"
 #include "orbx_internal.h"
 #include "orbx_mappoint.cuh"
 #include "orbx_posemath.cuh"
@@ -26,80 +25,52 @@
 using namespace orbx;
 
 namespace {
-thread_local std::string g_merr;
-int mfail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  g_merr = buf;
-  return code;
-}
+thread_local ErrorSlot g_merr;  // the orbm_ family's last error
 }  // namespace
 
-extern "C" const char* orbm_last_error(void) { return g_merr.c_str(); }
-
-#define MHIP(expr)                                                                             \
-  do {                                                                                         \
-    hipError_t e_ = (expr);                                                                    \
-    if (e_ != hipSuccess) return mfail(ORBX_EDEVICE, "%s: %s", #expr, hipGetErrorString(e_));  \
-  } while (0)
+extern "C" const char* orbm_last_error(void) { return g_merr.msg.c_str(); }
 
 struct orbx_matcher {
   int device = 0, max_pairs = 0, max_kps = 0;
   int sortn = 1;
-  int* init_ws = nullptr;  // SearchForInitialization: per-pair records, keys (init_ws_bytes_per_pair)
+  DeviceBuf init_ws;  // SearchForInitialization: per-pair records, keys (init_ws_bytes_per_pair)
   size_t init_ws_pair = 0;  // bytes per pair
-  int* host_init_ws = nullptr;  // orbm_search_for_initialization's own (its pitch is the call's)
-  size_t host_init_ws_bytes = 0;
-  int* err = nullptr;
-  int* stereo_sad = nullptr;  // [max_pairs][max_kps] SAD per left keypoint (-1 = none)
-  int* bow_hist = nullptr;    // [max_pairs][32] SearchByBoW rotation histogram (+ match count), 0 between calls
-  int* bow_rec = nullptr;     // [max_pairs][max_kps] SearchByBoW row records, -1 between calls
-  bool bow_clean = false;     // bow_hist / bow_rec hold their between-calls values
-  int* pose_picks = nullptr;  // pose-projection picks per point (frames x mp_pitch)
-  size_t pose_picks_cap = 0;
-  uint8_t* view_ws = nullptr;  // SearchLocalPoints: isInFrustum records, then the points in view compacted
-  size_t view_ws_bytes = 0;
-  uint8_t* refresh_ws = nullptr;  // RefreshMapPoints: class counters and work lists
-  size_t refresh_ws_bytes = 0;
-  uint8_t* po_ws = nullptr;  // PoseOptimization: edge records of frame pitches above kPoLdsEdges
-  size_t po_ws_bytes = 0;
+  DeviceBuf host_init_ws;  // orbm_search_for_initialization's own (its pitch is the call's; grows)
+  DeviceBuf err;
+  DeviceBuf stereo_sad;    // [max_pairs][max_kps] SAD per left keypoint (-1 = none)
+  DeviceBuf bow_hist;      // [max_pairs][32] SearchByBoW rotation histogram (+ match count), 0 between calls
+  DeviceBuf bow_rec;       // [max_pairs][max_kps] SearchByBoW row records, -1 between calls
+  bool bow_clean = false;  // bow_hist / bow_rec hold their between-calls values
+  // grown on demand, each after a wait for the workspace's last user (ws)
+  DeviceBuf pose_picks;  // pose-projection picks per point (frames x mp_pitch)
+  DeviceBuf view_ws;     // SearchLocalPoints: isInFrustum records, then the points in view compacted
+  DeviceBuf refresh_ws;  // RefreshMapPoints: class counters and work lists
+  DeviceBuf po_ws;       // PoseOptimization: edge records of frame pitches above kPoLdsEdges
   hipStream_t stream = nullptr;
   WsOrder ws;  // stream order of cand / stereo_sad / pose_picks / view_ws / refresh_ws / po_ws / bow_* across caller streams
   // streams of the launches that may set `err` (top-2, SearchByBoW, SearchLocalPoints, RefreshMapPoints, PoseOptimization)
   StreamMarks errm;
   // staging for the synchronous entry points
-  void* stage = nullptr;
-  size_t stage_bytes = 0;
-  void* h_stage = nullptr;  // pinned host staging (orbm_compute_stereo_matches_last)
-  size_t h_stage_bytes = 0;
+  DeviceBuf stage;
+  PinnedBuf h_stage;  // orbm_compute_stereo_matches_last
 };
 
+// the growth of the two stagings, with the messages their own hipMalloc lines gave
 static int stage_reserve(orbx_matcher* m, size_t bytes) {
-  if (m->stage_bytes >= bytes) return ORBX_OK;
-  if (m->stage) (void)hipFree(m->stage);
-  m->stage = nullptr;
-  m->stage_bytes = 0;
-  MHIP(hipMalloc(&m->stage, bytes));
-  m->stage_bytes = bytes;
-  return ORBX_OK;
+  const hipError_t e = m->stage.reserve(bytes);
+  return e == hipSuccess ? ORBX_OK
+                         : g_merr.fail(ORBX_EDEVICE, "hipMalloc(&m->stage, bytes): %s", hipGetErrorString(e));
 }
-
 static int host_stage_reserve(orbx_matcher* m, size_t bytes) {
-  if (m->h_stage_bytes >= bytes) return ORBX_OK;
-  if (m->h_stage) (void)hipHostFree(m->h_stage);
-  m->h_stage = nullptr;
-  m->h_stage_bytes = 0;
-  MHIP(hipHostMalloc(&m->h_stage, bytes, hipHostMallocDefault));
-  m->h_stage_bytes = bytes;
-  return ORBX_OK;
+  const hipError_t e = m->h_stage.reserve(bytes);
+  return e == hipSuccess ? ORBX_OK
+                         : g_merr.fail(ORBX_EDEVICE, "hipHostMalloc(&m->h_stage, bytes, hipHostMallocDefault): %s",
+                                       hipGetErrorString(e));
 }
 
 // the handle's own stream (status polls and the synchronous entry points), created on first use
 static int matcher_stream(orbx_matcher* m, hipStream_t* st) {
-  if (!m->stream) MHIP(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
+  if (!m->stream) HIP_OK(g_merr, hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
   *st = m->stream;
   return ORBX_OK;
 }
@@ -137,7 +108,7 @@ struct Stage {
   }
   template <class T>
   Slot<T> slot(size_t count) {
-    const Slot<T> s{&m->stage, used};
+    const Slot<T> s{&m->stage.p, used};
     used += (count * sizeof(T) + 255) & ~(size_t)255;
     return s;
   }
@@ -150,7 +121,7 @@ struct Stage {
   int copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
     if (!bytes || !src) return ORBX_OK;
     pending = true;
-    MHIP(hipMemcpyAsync(dst, src, bytes, kind, st));
+    HIP_OK(g_merr, hipMemcpyAsync(dst, src, bytes, kind, st));
     return ORBX_OK;
   }
   template <class T>
@@ -163,7 +134,7 @@ struct Stage {
   }
   int finish() {
     pending = false;
-    MHIP(hipStreamSynchronize(st));
+    HIP_OK(g_merr, hipStreamSynchronize(st));
     return ORBX_OK;
   }
 };
@@ -192,38 +163,37 @@ static int search_init_launch(orbx_matcher* m, const orbx_kp* d_kp1, const uint8
   P.nnratio = nnratio;
   P.check_ori = check_ori;
   P.kp_pitch = kp_pitch;
-  if (m->ws.before((hipStream_t)stream)) return mfail(ORBX_EDEVICE, "stream wait on the workspace failed");
+  if (m->ws.before((hipStream_t)stream)) return g_merr.fail(ORBX_EDEVICE, "stream wait on the workspace failed");
   const int rc = launch_search_init(P, d_kp1, d_desc1, d_n1, d_kp2, d_desc2, d_n2, d_prev_xy, ws, d_matches12,
                                     d_nmatches, pairs, stream);
-  if (!rc && m->ws.after((hipStream_t)stream)) return mfail(ORBX_EDEVICE, "event record failed");
+  if (!rc && m->ws.after((hipStream_t)stream)) return g_merr.fail(ORBX_EDEVICE, "event record failed");
   if (rc == ORBX_ECAPACITY)
-    return mfail(ORBX_ECAPACITY, "kp_pitch %d too large for SearchForInitialization at nnratio %g (<= %d)", kp_pitch,
+    return g_merr.fail(ORBX_ECAPACITY, "kp_pitch %d too large for SearchForInitialization at nnratio %g (<= %d)", kp_pitch,
                  (double)nnratio, search_init_max_pitch(nnratio));
-  if (rc) return mfail(ORBX_EDEVICE, "search_init launch: %s", hipGetErrorString(hipGetLastError()));
+  if (rc) return g_merr.fail(ORBX_EDEVICE, "search_init launch: %s", hipGetErrorString(hipGetLastError()));
   return ORBX_OK;
 }
 
 extern "C" {
 
 int orbm_create(int device, int max_pairs, int max_kps, orbm_handle* out) {
-  if (!out || max_pairs < 1 || max_kps < 1) return mfail(ORBX_EINVAL, "bad argument");
-  if (max_kps > 65535) return mfail(ORBX_EINVAL, "max_kps must be <= 65535");
-  MHIP(hipSetDevice(device));
+  if (!out || max_pairs < 1 || max_kps < 1) return g_merr.fail(ORBX_EINVAL, "bad argument");
+  if (max_kps > 65535) return g_merr.fail(ORBX_EINVAL, "max_kps must be <= 65535");
+  HIP_OK(g_merr, hipSetDevice(device));
   orbx_matcher* m = new orbx_matcher();
   m->device = device;
   m->max_pairs = max_pairs;
   m->max_kps = max_kps;
   while (m->sortn < max_kps) m->sortn <<= 1;
   m->init_ws_pair = init_ws_bytes_per_pair(max_kps);
-  if (hipMalloc(&m->init_ws, (size_t)max_pairs * m->init_ws_pair) != hipSuccess ||
-      hipMalloc(&m->err, 16) != hipSuccess ||
-      hipMalloc(&m->stereo_sad, (size_t)max_pairs * max_kps * 4) != hipSuccess ||
-      hipMalloc(&m->bow_hist, (size_t)max_pairs * 32 * 4) != hipSuccess ||
-      hipMalloc(&m->bow_rec, (size_t)max_pairs * max_kps * 4) != hipSuccess) {
+  if (m->init_ws.alloc((size_t)max_pairs * m->init_ws_pair) != hipSuccess || m->err.alloc(16) != hipSuccess ||
+      m->stereo_sad.alloc((size_t)max_pairs * max_kps * 4) != hipSuccess ||
+      m->bow_hist.alloc((size_t)max_pairs * 32 * 4) != hipSuccess ||
+      m->bow_rec.alloc((size_t)max_pairs * max_kps * 4) != hipSuccess) {
     orbm_destroy(m);
-    return mfail(ORBX_ENOMEM, "matcher workspace allocation failed");
+    return g_merr.fail(ORBX_ENOMEM, "matcher workspace allocation failed");
   }
-  (void)hipMemset(m->err, 0, 16);
+  (void)hipMemset(m->err.as<int>(), 0, 16);
   *out = m;
   return ORBX_OK;
 }
@@ -236,38 +206,31 @@ int orbm_destroy(orbm_handle m) {
   m->ws.release();
   (void)m->errm.wait();
   m->errm.release();
-  if (m->init_ws) (void)hipFree(m->init_ws);
-  if (m->host_init_ws) (void)hipFree(m->host_init_ws);
-  if (m->err) (void)hipFree(m->err);
-  if (m->stereo_sad) (void)hipFree(m->stereo_sad);
-  if (m->bow_hist) (void)hipFree(m->bow_hist);
-  if (m->bow_rec) (void)hipFree(m->bow_rec);
-  if (m->pose_picks) (void)hipFree(m->pose_picks);
-  if (m->view_ws) (void)hipFree(m->view_ws);
-  if (m->refresh_ws) (void)hipFree(m->refresh_ws);
-  if (m->po_ws) (void)hipFree(m->po_ws);
-  if (m->stage) (void)hipFree(m->stage);
-  if (m->h_stage) (void)hipHostFree(m->h_stage);
+  // the buffers go before the stream, not with the handle after it
+  for (DeviceBuf* b : {&m->init_ws, &m->host_init_ws, &m->err, &m->stereo_sad, &m->bow_hist, &m->bow_rec, &m->pose_picks,
+                       &m->view_ws, &m->refresh_ws, &m->po_ws, &m->stage})
+    b->release();
+  m->h_stage.release();
   if (m->stream) (void)hipStreamDestroy(m->stream);
   delete m;
   return ORBX_OK;
 }
 
 int orbm_get_status(orbm_handle m, int reset, int* status) {
-  if (!m || !status) return mfail(ORBX_EINVAL, "null argument");
-  MHIP(hipSetDevice(m->device));
+  if (!m || !status) return g_merr.fail(ORBX_EINVAL, "null argument");
+  HIP_OK(g_merr, hipSetDevice(m->device));
   // the kernels that set the word ran on caller streams: wait for those
   // launches (their stream marks), not for the device
-  if (m->errm.wait()) return mfail(ORBX_EDEVICE, "status: event wait failed");
+  if (m->errm.wait()) return g_merr.fail(ORBX_EDEVICE, "status: event wait failed");
   hipStream_t st;
   int rc;
   if ((rc = matcher_stream(m, &st))) return rc;
   int e = 0;
-  MHIP(hipMemcpyAsync(&e, m->err, 4, hipMemcpyDeviceToHost, st));
-  MHIP(hipStreamSynchronize(st));
+  HIP_OK(g_merr, hipMemcpyAsync(&e, m->err.as<int>(), 4, hipMemcpyDeviceToHost, st));
+  HIP_OK(g_merr, hipStreamSynchronize(st));
   if (reset && e) {
-    MHIP(hipMemsetAsync(m->err, 0, 16, st));
-    MHIP(hipStreamSynchronize(st));
+    HIP_OK(g_merr, hipMemsetAsync(m->err.as<int>(), 0, 16, st));
+    HIP_OK(g_merr, hipStreamSynchronize(st));
   }
   *status = e;
   return ORBX_OK;
@@ -282,13 +245,13 @@ int orbm_descriptor_distance(const uint8_t* a, const uint8_t* b) {
 int orbm_hamming_top2(orbm_handle m, const uint8_t* d_A, size_t a_pitch, const int* d_nA, int a_cap,
                       const uint8_t* d_B, size_t b_pitch, const int* d_nB, int pairs, int* d_best_idx, int* d_best,
                       int* d_second, void* stream) {
-  if (!m || !d_A || !d_B || !d_nA || !d_nB || pairs < 1) return mfail(ORBX_EINVAL, "bad argument");
-  if ((a_pitch | b_pitch) & 15) return mfail(ORBX_EINVAL, "pitches must be multiples of 16 bytes");
-  MHIP(hipSetDevice(m->device));
+  if (!m || !d_A || !d_B || !d_nA || !d_nB || pairs < 1) return g_merr.fail(ORBX_EINVAL, "bad argument");
+  if ((a_pitch | b_pitch) & 15) return g_merr.fail(ORBX_EINVAL, "pitches must be multiples of 16 bytes");
+  HIP_OK(g_merr, hipSetDevice(m->device));
   const int rc = launch_hamming_top2(d_A, a_pitch, d_nA, a_cap, d_B, b_pitch, d_nB, pairs, d_best_idx, d_best,
-                                     d_second, m->err, stream);
-  if (rc) return mfail(rc, "launch failed");
-  return m->errm.mark((hipStream_t)stream) ? mfail(ORBX_EDEVICE, "event record failed") : ORBX_OK;
+                                     d_second, m->err.as<int>(), stream);
+  if (rc) return g_merr.fail(rc, "launch failed");
+  return m->errm.mark((hipStream_t)stream) ? g_merr.fail(ORBX_EDEVICE, "event record failed") : ORBX_OK;
 }
 
 int orbm_search_for_initialization_batch(orbm_handle m, const orbx_kp* d_kp1, const uint8_t* d_desc1,
@@ -297,20 +260,20 @@ int orbm_search_for_initialization_batch(orbm_handle m, const orbx_kp* d_kp1, co
                                          float* d_prev_xy, int window, float nnratio, int check_ori,
                                          int* d_matches12, int* d_nmatches, void* stream) {
   if (!m || pairs < 1 || pairs > m->max_pairs || kp_pitch < 1 || kp_pitch > m->max_kps)
-    return mfail(ORBX_EINVAL, "pairs/kp_pitch exceed the matcher workspace");
-  MHIP(hipSetDevice(m->device));
+    return g_merr.fail(ORBX_EINVAL, "pairs/kp_pitch exceed the matcher workspace");
+  HIP_OK(g_merr, hipSetDevice(m->device));
   return search_init_launch(m, d_kp1, d_desc1, d_n1, d_kp2, d_desc2, d_n2, kp_pitch, pairs, b, d_prev_xy, window,
-                            nnratio, check_ori, d_matches12, d_nmatches, stream, m->init_ws);
+                            nnratio, check_ori, d_matches12, d_nmatches, stream, m->init_ws.as<int>());
 }
 
 int orbm_search_for_initialization(orbm_handle m, const orbx_kp* kp1, const uint8_t* desc1, int n1,
                                    const orbx_kp* kp2, const uint8_t* desc2, int n2, orbm_grid_bounds bounds,
                                    float* prev_xy, int window, float nnratio, int check_ori, int* matches12,
                                    int* nmatches) {
-  if (!m || !nmatches || n1 < 0 || n2 < 0) return mfail(ORBX_EINVAL, "bad argument");
+  if (!m || !nmatches || n1 < 0 || n2 < 0) return g_merr.fail(ORBX_EINVAL, "bad argument");
   if ((n1 && (!kp1 || !desc1 || !prev_xy || !matches12)) || (n2 && (!kp2 || !desc2)))
-    return mfail(ORBX_EINVAL, "null array");
-  MHIP(hipSetDevice(m->device));
+    return g_merr.fail(ORBX_EINVAL, "null array");
+  HIP_OK(g_merr, hipSetDevice(m->device));
   // Only octave-0 keypoints take part (src/ORBmatcher.cc:424-428: level1 > 0 is
   // skipped; GetFeaturesInArea(.., level1, level1) returns octave-0 keypoints of
   // F2, src/Frame.cc:350-352), so both frames are compacted to them in index
@@ -332,7 +295,7 @@ int orbm_search_for_initialization(orbm_handle m, const orbx_kp* kp1, const uint
     return ORBX_OK;
   }
   const int pitch = std::max(c1, c2);
-  if (pitch > 65535) return mfail(ORBX_ECAPACITY, "more than 65535 octave-0 keypoints");
+  if (pitch > 65535) return g_merr.fail(ORBX_ECAPACITY, "more than 65535 octave-0 keypoints");
   std::vector<orbx_kp> hk((size_t)c1 + c2);
   std::vector<uint8_t> hd(((size_t)c1 + c2) * 32);
   std::vector<float> hp((size_t)c1 * 2);
@@ -362,18 +325,13 @@ int orbm_search_for_initialization(orbm_handle m, const orbx_kp* kp1, const uint
     return rc;
   // the call's own workspace, sized for its pitch (the octave-0 counts)
   const size_t wsb = init_ws_bytes_per_pair(pitch);
-  if (wsb > m->host_init_ws_bytes) {
-    if (m->host_init_ws) {
-      MHIP(hipStreamSynchronize(st.st));
-      (void)hipFree(m->host_init_ws);
-    }
-    m->host_init_ws = nullptr;
-    m->host_init_ws_bytes = 0;
-    MHIP(hipMalloc(&m->host_init_ws, wsb));
-    m->host_init_ws_bytes = wsb;
+  if (wsb > m->host_init_ws.n) {
+    if (m->host_init_ws.p) HIP_OK(g_merr, hipStreamSynchronize(st.st));
+    if (const hipError_t e = m->host_init_ws.reserve(wsb))
+      return g_merr.fail(ORBX_EDEVICE, "hipMalloc(&m->host_init_ws, wsb): %s", hipGetErrorString(e));
   }
   rc = search_init_launch(m, dk1, dd1, dn, dk2, dd2, dn + 1, pitch, 1, bounds, dprev, window, nnratio, check_ori, dm,
-                          dnm, st.st, m->host_init_ws);
+                          dnm, st.st, m->host_init_ws.as<int>());
   if (rc || (rc = st.down(&nm, dnm, 1)) || (rc = st.down(hm.data(), dm, c1)) ||
       (rc = st.down(hp.data(), dprev, (size_t)c1 * 2)) || (rc = st.finish()))
     return rc;
@@ -391,7 +349,7 @@ int orbm_search_by_bow(orbm_handle m, const uint8_t* descA, const float* angleA,
                        orbm_feature_vector fvA, const uint8_t* descB, const float* angleB, const uint8_t* mpB,
                        int nB, orbm_feature_vector fvB, float nnratio, int check_ori, int kf_vs_kf, int* out,
                        int* nmatches) {
-  if (!m || !nmatches || nA < 0 || nB < 0) return mfail(ORBX_EINVAL, "bad argument");
+  if (!m || !nmatches || nA < 0 || nB < 0) return g_merr.fail(ORBX_EINVAL, "bad argument");
   // DBoW2 precondition: each feature sits in at most one node; node ids ascending
   auto check_fv = [&](const orbm_feature_vector& fv, int n) -> bool {
     std::vector<char> seen(std::max(n, 1), 0);
@@ -407,11 +365,11 @@ int orbm_search_by_bow(orbm_handle m, const uint8_t* descA, const float* angleA,
   };
   // the row records keep the matched index in 16 bits (bin << 16 | index):
   // B's index in KF-KF mode, A's in KF-Frame mode; B's candidates are 16-bit too
-  if (nB > 65536) return mfail(ORBX_EINVAL, "nB must be <= 65536");
-  if (!kf_vs_kf && nA > 65536) return mfail(ORBX_EINVAL, "nA must be <= 65536 (KF-Frame row records)");
+  if (nB > 65536) return g_merr.fail(ORBX_EINVAL, "nB must be <= 65536");
+  if (!kf_vs_kf && nA > 65536) return g_merr.fail(ORBX_EINVAL, "nA must be <= 65536 (KF-Frame row records)");
   if (!check_fv(fvA, nA) || !check_fv(fvB, nB))
-    return mfail(ORBX_EINVAL, "FeatureVector must have ascending node ids and disjoint in-range indices");
-  MHIP(hipSetDevice(m->device));
+    return g_merr.fail(ORBX_EINVAL, "FeatureVector must have ascending node ids and disjoint in-range indices");
+  HIP_OK(g_merr, hipSetDevice(m->device));
   const int nout = kf_vs_kf ? nA : nB;
   const int ia = fvA.n_nodes ? fvA.off[fvA.n_nodes] : 0, ib = fvB.n_nodes ? fvB.off[fvB.n_nodes] : 0;
   const int pitch = std::max(nout, 1);  // out / records: the launch's pitch
@@ -439,9 +397,9 @@ int orbm_search_by_bow(orbm_handle m, const uint8_t* descA, const float* angleA,
   BowSide B{ddB, dgB, 1, mpB ? (uint8_t*)dmB : nullptr, dn + 1, dnoB, dofB, dixB, dn + 3, 0, 0};
   bool clean = false;  // staging memory: records and histogram filled first
   if ((rc = launch_search_bow(A, B, 1, nnratio, check_ori, kf_vs_kf, dout, pitch, dnm, drec, (size_t)pitch, dhist, 32,
-                              &clean, m->err, st.st)))
-    return mfail(rc, "search_bow launch: %s", hipGetErrorString(hipGetLastError()));
-  if (m->errm.mark(st.st)) return mfail(ORBX_EDEVICE, "event record failed");
+                              &clean, m->err.as<int>(), st.st)))
+    return g_merr.fail(rc, "search_bow launch: %s", hipGetErrorString(hipGetLastError()));
+  if (m->errm.mark(st.st)) return g_merr.fail(ORBX_EDEVICE, "event record failed");
   if ((rc = st.down(&nm, dnm, 1)) || (rc = st.down(out, dout, nout)) || (rc = st.finish())) return rc;
   *nmatches = nm;
   return ORBX_OK;
@@ -456,21 +414,22 @@ int orbm_search_by_bow_batch(orbm_handle m, int pairs, int kp_pitch, int node_pi
   if (!m || pairs < 1 || kp_pitch < 1 || node_pitch < 1 || !d_kpA || !d_descA || !d_nA || !d_nodesA || !d_offA ||
       !d_idxA || !d_nnA || !d_kpB || !d_descB || !d_nB || !d_nodesB || !d_offB || !d_idxB || !d_nnB || !d_out ||
       !d_nmatches)
-    return mfail(ORBX_EINVAL, "bad argument");
+    return g_merr.fail(ORBX_EINVAL, "bad argument");
   if (pairs > m->max_pairs || kp_pitch > m->max_kps)
-    return mfail(ORBX_ECAPACITY, "pairs/kp_pitch above the matcher's max_pairs/max_kps");
-  if (kp_pitch > 65536) return mfail(ORBX_EINVAL, "kp_pitch must be <= 65536");
-  MHIP(hipSetDevice(m->device));
+    return g_merr.fail(ORBX_ECAPACITY, "pairs/kp_pitch above the matcher's max_pairs/max_kps");
+  if (kp_pitch > 65536) return g_merr.fail(ORBX_EINVAL, "kp_pitch must be <= 65536");
+  HIP_OK(g_merr, hipSetDevice(m->device));
   // angles straight from the orbx_kp records (cv::KeyPoint::angle, float 3 of 7)
   BowSide A{d_descA, (const float*)d_kpA + 3, 7, d_mpA, d_nA, d_nodesA, d_offA, d_idxA, d_nnA, kp_pitch, node_pitch};
   BowSide B{d_descB, (const float*)d_kpB + 3, 7, d_mpB, d_nB, d_nodesB, d_offB, d_idxB, d_nnB, kp_pitch, node_pitch};
   hipStream_t s = (hipStream_t)stream;
-  if (m->ws.before(s)) return mfail(ORBX_EDEVICE, "stream wait on the workspace failed");
-  const int rc = launch_search_bow(A, B, pairs, nnratio, check_ori, kf_vs_kf, d_out, kp_pitch, d_nmatches, m->bow_rec,
-                                   (size_t)m->max_pairs * m->max_kps, m->bow_hist, (size_t)m->max_pairs * 32,
-                                   &m->bow_clean, m->err, stream);
-  if (rc) return mfail(rc, "search_bow launch: %s", hipGetErrorString(hipGetLastError()));
-  if (m->ws.after(s) || m->errm.mark(s)) return mfail(ORBX_EDEVICE, "event record failed");
+  if (m->ws.before(s)) return g_merr.fail(ORBX_EDEVICE, "stream wait on the workspace failed");
+  const int rc = launch_search_bow(A, B, pairs, nnratio, check_ori, kf_vs_kf, d_out, kp_pitch, d_nmatches,
+                                   m->bow_rec.as<int>(),
+                                   (size_t)m->max_pairs * m->max_kps, m->bow_hist.as<int>(), (size_t)m->max_pairs * 32,
+                                   &m->bow_clean, m->err.as<int>(), stream);
+  if (rc) return g_merr.fail(rc, "search_bow launch: %s", hipGetErrorString(hipGetLastError()));
+  if (m->ws.after(s) || m->errm.mark(s)) return g_merr.fail(ORBX_EDEVICE, "event record failed");
   return ORBX_OK;
 }
 
@@ -483,20 +442,20 @@ static int stereo_batch(orbm_handle m, orbx_handle left, int left_frame0, orbx_h
                         float* d_uRight, float* d_depth, int* d_nkept, void* stream, bool sync) {
   if (!m || !left || !right || !d_kpL || !d_descL || !d_nL || !d_kpR || !d_descR || !d_nR || !d_uRight ||
       !d_depth || !d_nkept || pairs < 1 || kp_pitch < 1)
-    return mfail(ORBX_EINVAL, "bad argument");
+    return g_merr.fail(ORBX_EINVAL, "bad argument");
   if (pairs > m->max_pairs || kp_pitch > m->max_kps)
-    return mfail(ORBX_ECAPACITY, "pairs/kp_pitch above the matcher's max_pairs/max_kps");
-  if (!(mb > 0.f)) return mfail(ORBX_EINVAL, "baseline mb must be positive");
-  MHIP(hipSetDevice(m->device));
+    return g_merr.fail(ORBX_ECAPACITY, "pairs/kp_pitch above the matcher's max_pairs/max_kps");
+  if (!(mb > 0.f)) return g_merr.fail(ORBX_EINVAL, "baseline mb must be positive");
+  HIP_OK(g_merr, hipSetDevice(m->device));
   StereoParams P{};
   int wr[kMaxLevels], hr[kMaxLevels], LR = 0;
   float sr[kMaxLevels], isr[kMaxLevels];
   if (extractor_pyramid(left, left_frame0, pairs, &P.pl, P.lw, P.lh, P.scale, P.inv_scale, &P.L) ||
       extractor_pyramid(right, right_frame0, pairs, &P.pr, wr, hr, sr, isr, &LR))
-    return mfail(ORBX_EINVAL, "stereo pyramid: %s", orbx_last_error());
-  if (LR != P.L) return mfail(ORBX_EINVAL, "left and right extractors have different level counts");
+    return g_merr.fail(ORBX_EINVAL, "stereo pyramid: %s", orbx_last_error());
+  if (LR != P.L) return g_merr.fail(ORBX_EINVAL, "left and right extractors have different level counts");
   for (int l = 0; l < P.L; ++l)
-    if (wr[l] != P.lw[l] || hr[l] != P.lh[l]) return mfail(ORBX_EINVAL, "left and right image sizes differ");
+    if (wr[l] != P.lw[l] || hr[l] != P.lh[l]) return g_merr.fail(ORBX_EINVAL, "left and right image sizes differ");
   P.nrows = P.lh[0];
   P.kp_pitch = kp_pitch;
   P.mb = mb;
@@ -515,7 +474,7 @@ static int stereo_batch(orbm_handle m, orbx_handle left, int left_frame0, orbx_h
   // workgroup g takes left keypoints iL = g + groups * m: at most this many
   P.jobs_cap = (kp_pitch + P.groups - 1) / P.groups;
   if (stereo_lds_bytes(P.nrows, kp_pitch, P.jobs_cap) > 156 * 1024)
-    return mfail(ORBX_ECAPACITY, "stereo row table does not fit in LDS (rows %d, kp_pitch %d)", P.nrows, kp_pitch);
+    return g_merr.fail(ORBX_ECAPACITY, "stereo row table does not fit in LDS (rows %d, kp_pitch %d)", P.nrows, kp_pitch);
   // the SAD scratch is the matcher's, the pyramids the extractors': order
   // this launch after their last users and make their next users wait for it
   hipStream_t s = (hipStream_t)stream;
@@ -523,11 +482,12 @@ static int stereo_batch(orbm_handle m, orbx_handle left, int left_frame0, orbx_h
   WsOrder* wr2 = extractor_ws(right);
   if (sync ? (m->ws.before_pending(s) || wl->before_pending(s) || wr2->before_pending(s))
            : (m->ws.before(s) || wl->before(s) || wr2->before(s)))
-    return mfail(ORBX_EDEVICE, "stream wait on the workspaces failed");
-  if (launch_stereo(P, d_kpL, d_descL, d_nL, d_kpR, d_descR, d_nR, pairs, d_uRight, d_depth, m->stereo_sad, d_nkept,
+    return g_merr.fail(ORBX_EDEVICE, "stream wait on the workspaces failed");
+  if (launch_stereo(P, d_kpL, d_descL, d_nL, d_kpR, d_descR, d_nR, pairs, d_uRight, d_depth, m->stereo_sad.as<int>(),
+                    d_nkept,
                     stream) != ORBX_OK)
-    return mfail(ORBX_EDEVICE, "stereo launch: %s", hipGetErrorString(hipGetLastError()));
-  if (!sync && (m->ws.after(s) || wl->after(s) || wr2->after(s))) return mfail(ORBX_EDEVICE, "event record failed");
+    return g_merr.fail(ORBX_EDEVICE, "stereo launch: %s", hipGetErrorString(hipGetLastError()));
+  if (!sync && (m->ws.after(s) || wl->after(s) || wr2->after(s))) return g_merr.fail(ORBX_EDEVICE, "event record failed");
   return ORBX_OK;
 }
 
@@ -544,10 +504,10 @@ int orbm_compute_stereo_matches(orbm_handle m, orbx_handle left, orbx_handle rig
                                 const uint8_t* descL, int nL, const orbx_kp* kpR, const uint8_t* descR, int nR,
                                 float mb, float mbf, float* uRight, float* depth, int* nkept) {
   if (!m || !nkept || nL < 0 || nR < 0 || (nL && (!kpL || !descL || !uRight || !depth)) || (nR && (!kpR || !descR)))
-    return mfail(ORBX_EINVAL, "bad argument");
-  if (nL > m->max_kps || nR > m->max_kps) return mfail(ORBX_ECAPACITY, "more keypoints than max_kps");
-  if (nR > 65535) return mfail(ORBX_ECAPACITY, "more than 65535 right keypoints");
-  MHIP(hipSetDevice(m->device));
+    return g_merr.fail(ORBX_EINVAL, "bad argument");
+  if (nL > m->max_kps || nR > m->max_kps) return g_merr.fail(ORBX_ECAPACITY, "more keypoints than max_kps");
+  if (nR > 65535) return g_merr.fail(ORBX_ECAPACITY, "more than 65535 right keypoints");
+  HIP_OK(g_merr, hipSetDevice(m->device));
   const int pitch = std::max(std::max(nL, nR), 1);
   const int hn[2] = {nL, nR};
   int kept = 0, rc;
@@ -579,14 +539,14 @@ struct StereoBlock {
     b->bytes = 16 + (size_t)cap * 8;
     int rc;
     if ((rc = stage_reserve(m, b->bytes)) || (rc = host_stage_reserve(m, b->bytes))) return rc;
-    b->kept = (int*)m->stage;
-    b->uRight = (float*)m->stage + 4;
+    b->kept = m->stage.as<int>();
+    b->uRight = m->stage.as<float>() + 4;
     b->depth = b->uRight + cap;
     return ORBX_OK;
   }
   // from the pinned copy, the first nL of each array
   static void unpack(const orbx_matcher* m, int cap, int nL, float* uRight, float* depth, int* nkept) {
-    const uint8_t* h = (const uint8_t*)m->h_stage;
+    const uint8_t* h = m->h_stage.as<const uint8_t>();
     *nkept = ((const int*)h)[0];
     if (nL) {
       memcpy(uRight, h + 16, (size_t)nL * 4);
@@ -601,40 +561,40 @@ struct StereoBlock {
 // and mvDepth cross the link.
 int orbm_compute_stereo_matches_last(orbm_handle m, orbx_handle left, orbx_handle right, float mb, float mbf,
                                      float* uRight, float* depth, int nL, int* nkept) {
-  if (!m || !left || !right || !nkept || nL < 0 || (nL && (!uRight || !depth))) return mfail(ORBX_EINVAL, "bad argument");
+  if (!m || !left || !right || !nkept || nL < 0 || (nL && (!uRight || !depth))) return g_merr.fail(ORBX_EINVAL, "bad argument");
   const int* dnL = nullptr;
   const int* dnR = nullptr;
   const orbx_kp *dkl = nullptr, *dkr = nullptr;
   const uint8_t *ddl = nullptr, *ddr = nullptr;
   int capL = 0, capR = 0;
   if (extractor_last_output(left, &dnL, &dkl, &ddl, &capL) || extractor_last_output(right, &dnR, &dkr, &ddr, &capR))
-    return mfail(ORBX_EINVAL, "stereo (last extraction): %s", orbx_last_error());
+    return g_merr.fail(ORBX_EINVAL, "stereo (last extraction): %s", orbx_last_error());
   if (!dnL || !dnR) {
     // an empty left or right image: no right keypoints to match, every left
     // keypoint keeps uRight = depth = -1 (src/Frame.cc:465-470)
-    if (!dnL && nL) return mfail(ORBX_EINVAL, "nL %d but the left extraction was of an empty image", nL);
+    if (!dnL && nL) return g_merr.fail(ORBX_EINVAL, "nL %d but the left extraction was of an empty image", nL);
     for (int i = 0; i < nL; ++i) uRight[i] = depth[i] = -1.f;
     *nkept = 0;
     return ORBX_OK;
   }
-  if (capL != capR) return mfail(ORBX_EINVAL, "left and right extractors have different capacities");
-  if (nL > capL) return mfail(ORBX_EINVAL, "nL %d above the left extraction's capacity %d", nL, capL);
-  MHIP(hipSetDevice(m->device));
+  if (capL != capR) return g_merr.fail(ORBX_EINVAL, "left and right extractors have different capacities");
+  if (nL > capL) return g_merr.fail(ORBX_EINVAL, "nL %d above the left extraction's capacity %d", nL, capL);
+  HIP_OK(g_merr, hipSetDevice(m->device));
   // the device path sizes its LDS by the extractors' capacity; past the
   // matcher's limits (max_kps, or the stereo kernel's LDS for large
   // nFeatures) the keypoints come to the host and take the host-array path,
   // whose pitch is the actual counts
   auto host_fallback = [&]() -> int {
     int cnt[2] = {0, 0};
-    MHIP(hipMemcpy(&cnt[0], dnL, 4, hipMemcpyDeviceToHost));
-    MHIP(hipMemcpy(&cnt[1], dnR, 4, hipMemcpyDeviceToHost));
-    if (nL > cnt[0]) return mfail(ORBX_EINVAL, "nL %d above the left extraction's count %d", nL, cnt[0]);
+    HIP_OK(g_merr, hipMemcpy(&cnt[0], dnL, 4, hipMemcpyDeviceToHost));
+    HIP_OK(g_merr, hipMemcpy(&cnt[1], dnR, 4, hipMemcpyDeviceToHost));
+    if (nL > cnt[0]) return g_merr.fail(ORBX_EINVAL, "nL %d above the left extraction's count %d", nL, cnt[0]);
     std::vector<orbx_kp> kl(std::max(cnt[0], 1)), kr(std::max(cnt[1], 1));
     std::vector<uint8_t> dl((size_t)std::max(cnt[0], 1) * 32), dr((size_t)std::max(cnt[1], 1) * 32);
-    MHIP(hipMemcpy(kl.data(), dkl, (size_t)cnt[0] * sizeof(orbx_kp), hipMemcpyDeviceToHost));
-    MHIP(hipMemcpy(kr.data(), dkr, (size_t)cnt[1] * sizeof(orbx_kp), hipMemcpyDeviceToHost));
-    MHIP(hipMemcpy(dl.data(), ddl, (size_t)cnt[0] * 32, hipMemcpyDeviceToHost));
-    MHIP(hipMemcpy(dr.data(), ddr, (size_t)cnt[1] * 32, hipMemcpyDeviceToHost));
+    HIP_OK(g_merr, hipMemcpy(kl.data(), dkl, (size_t)cnt[0] * sizeof(orbx_kp), hipMemcpyDeviceToHost));
+    HIP_OK(g_merr, hipMemcpy(kr.data(), dkr, (size_t)cnt[1] * sizeof(orbx_kp), hipMemcpyDeviceToHost));
+    HIP_OK(g_merr, hipMemcpy(dl.data(), ddl, (size_t)cnt[0] * 32, hipMemcpyDeviceToHost));
+    HIP_OK(g_merr, hipMemcpy(dr.data(), ddr, (size_t)cnt[1] * 32, hipMemcpyDeviceToHost));
     return orbm_compute_stereo_matches(m, left, right, kl.data(), dl.data(), nL, kr.data(), dr.data(), cnt[1], mb, mbf,
                                        uRight, depth, nkept);
   };
@@ -647,7 +607,7 @@ int orbm_compute_stereo_matches_last(orbm_handle m, orbx_handle left, orbx_handl
                     blk.kept, st.st, true);
   if (rc == ORBX_ECAPACITY) return host_fallback();  // checked before any launch
   st.pending = true;  // no upload went before: the kernels count as enqueued even where stereo_batch failed
-  if (rc || (rc = st.copy(m->h_stage, blk.kept, blk.bytes, hipMemcpyDeviceToHost)) || (rc = st.finish())) return rc;
+  if (rc || (rc = st.copy(m->h_stage.p, blk.kept, blk.bytes, hipMemcpyDeviceToHost)) || (rc = st.finish())) return rc;
   StereoBlock::unpack(m, capL, nL, uRight, depth, nkept);
   return ORBX_OK;
 }
@@ -699,18 +659,18 @@ int orbm_stereo_frame(orbm_handle m, orbx_handle left, orbx_handle right, const 
                       float mbf, orbx_kp* kps_left, int cap_left, uint8_t* desc_left, int* n_left,
                       orbx_kp* kps_right, int cap_right, uint8_t* desc_right, int* n_right, float* uRight,
                       float* depth, int* nkept) {
-  if (!m || !left || !right || !n_left || !n_right || !nkept || w < 0 || h < 0) return mfail(ORBX_EINVAL, "bad argument");
-  if (left == right) return mfail(ORBX_EINVAL, "left and right need two extractor handles");
-  if (!(mb > 0.f)) return mfail(ORBX_EINVAL, "baseline mb must be positive");
+  if (!m || !left || !right || !n_left || !n_right || !nkept || w < 0 || h < 0) return g_merr.fail(ORBX_EINVAL, "bad argument");
+  if (left == right) return g_merr.fail(ORBX_EINVAL, "left and right need two extractor handles");
+  if (!(mb > 0.f)) return g_merr.fail(ORBX_EINVAL, "baseline mb must be positive");
   *nkept = 0;
   if (w == 0 || h == 0) {
     // empty images: the two calls' own semantics (no outputs, uRight = -1)
     if (orbx_extract(left, img_left, w, h, stride_left, kps_left, cap_left, desc_left, n_left) ||
         orbx_extract(right, img_right, w, h, stride_right, kps_right, cap_right, desc_right, n_right))
-      return mfail(ORBX_EINVAL, "stereo frame: %s", orbx_last_error());
+      return g_merr.fail(ORBX_EINVAL, "stereo frame: %s", orbx_last_error());
     return orbm_compute_stereo_matches_last(m, left, right, mb, mbf, uRight, depth, *n_left, nkept);
   }
-  MHIP(hipSetDevice(m->device));
+  HIP_OK(g_merr, hipSetDevice(m->device));
   int brc = ORBX_OK, cap = 0;
   auto between = [&](hipStream_t st) -> int {
     const int* dnL = nullptr;
@@ -719,8 +679,8 @@ int orbm_stereo_frame(orbm_handle m, orbx_handle left, orbx_handle right, const 
     const uint8_t *ddl = nullptr, *ddr = nullptr;
     int capR = 0;
     if (extractor_last_output(left, &dnL, &dkl, &ddl, &cap) || extractor_last_output(right, &dnR, &dkr, &ddr, &capR))
-      return brc = mfail(ORBX_EINVAL, "stereo frame: %s", orbx_last_error());
-    if (cap != capR) return brc = mfail(ORBX_EINVAL, "left and right extractors have different capacities");
+      return brc = g_merr.fail(ORBX_EINVAL, "stereo frame: %s", orbx_last_error());
+    if (cap != capR) return brc = g_merr.fail(ORBX_EINVAL, "left and right extractors have different capacities");
     // past the matcher's limits: the host-array path after the extractions
     if (cap > m->max_kps) return (brc = ORBX_ECAPACITY), ORBX_OK;
     StereoBlock blk;
@@ -730,7 +690,7 @@ int orbm_stereo_frame(orbm_handle m, orbx_handle left, orbx_handle right, const 
                       blk.kept, st, true);
     if (rc == ORBX_ECAPACITY) return (brc = ORBX_ECAPACITY), ORBX_OK;  // checked before any launch
     if (rc) return brc = rc;
-    if ((rc = copy_to_host_async(m->h_stage, blk.kept, blk.bytes, st))) return brc = mfail(rc, "%s", orbx_last_error());
+    if ((rc = copy_to_host_async(m->h_stage.p, blk.kept, blk.bytes, st))) return brc = g_merr.fail(rc, "%s", orbx_last_error());
     return ORBX_OK;
   };
   // ORBX_STEREO_PROF=1 (diagnostics): host phases per call, medians printed at exit
@@ -740,14 +700,14 @@ int orbm_stereo_frame(orbm_handle m, orbx_handle left, orbx_handle right, const 
   int rc = extract_pair(left, right, img_left, stride_left, img_right, stride_right, w, h, between, kps_left, cap_left,
                         desc_left, n_left, kps_right, cap_right, desc_right, n_right, prof ? st + 1 : nullptr);
   if (prof && !rc) stereo_prof().add(left, st);
-  if (rc) return brc ? brc : mfail(rc, "stereo frame: %s", orbx_last_error());
+  if (rc) return brc ? brc : g_merr.fail(rc, "stereo frame: %s", orbx_last_error());
   if (brc == ORBX_ECAPACITY)
     return orbm_compute_stereo_matches_last(m, left, right, mb, mbf, uRight, depth, *n_left, nkept);
   if (brc) return brc;
   const int nL = *n_left;
   const bool no_out = nL && (!uRight || !depth);
   StereoBlock::unpack(m, cap, no_out ? 0 : nL, uRight, depth, nkept);
-  return no_out ? mfail(ORBX_EINVAL, "null uRight/depth") : ORBX_OK;
+  return no_out ? g_merr.fail(ORBX_EINVAL, "null uRight/depth") : ORBX_OK;
 }
 
 int orbm_search_by_projection_batch(orbm_handle m, const orbx_kp* d_kps, const uint8_t* d_desc, const int* d_n,
@@ -757,11 +717,11 @@ int orbm_search_by_projection_batch(orbm_handle m, const orbx_kp* d_kps, const u
                                     float nnratio, int* d_out, int* d_nmatches, void* stream) {
   if (!m || !d_kps || !d_desc || !d_n || !scale || !d_blocked || !d_mps || !d_mpdesc || !d_nmp || !d_out ||
       !d_nmatches || frames < 1 || kp_pitch < 1 || mp_pitch < 1 || nlevels < 1 || nlevels > kMaxLevels)
-    return mfail(ORBX_EINVAL, "bad argument");
-  if (mp_pitch > 8192) return mfail(ORBX_ECAPACITY, "more than 8192 map points per frame");
-  if (!(b.max_x > b.min_x) || !(b.max_y > b.min_y)) return mfail(ORBX_EINVAL, "empty grid bounds");
-  if (proj_lds_bytes(kp_pitch) > 156 * 1024) return mfail(ORBX_ECAPACITY, "kp_pitch %d too large", kp_pitch);
-  MHIP(hipSetDevice(m->device));
+    return g_merr.fail(ORBX_EINVAL, "bad argument");
+  if (mp_pitch > 8192) return g_merr.fail(ORBX_ECAPACITY, "more than 8192 map points per frame");
+  if (!(b.max_x > b.min_x) || !(b.max_y > b.min_y)) return g_merr.fail(ORBX_EINVAL, "empty grid bounds");
+  if (proj_lds_bytes(kp_pitch) > 156 * 1024) return g_merr.fail(ORBX_ECAPACITY, "kp_pitch %d too large", kp_pitch);
+  HIP_OK(g_merr, hipSetDevice(m->device));
   ProjParams P{};
   set_grid_bounds(P, b);
   for (int l = 0; l < kMaxLevels; ++l) P.scale[l] = scale[std::min(l, nlevels - 1)];
@@ -775,17 +735,17 @@ int orbm_search_by_projection_batch(orbm_handle m, const orbx_kp* d_kps, const u
   static long long* prof = nullptr;  // ORBX_PROJ_PROF: phase clocks of frame 0 printed after the call
   const bool do_prof = getenv("ORBX_PROJ_PROF") != nullptr;
   if (do_prof) {
-    if (!prof) MHIP(hipMalloc(&prof, (size_t)frames * 64 * 8));
-    MHIP(hipMemset(prof, 0, (size_t)frames * 64 * 8));
+    if (!prof) HIP_OK(g_merr, hipMalloc(&prof, (size_t)frames * 64 * 8));
+    HIP_OK(g_merr, hipMemset(prof, 0, (size_t)frames * 64 * 8));
     P.prof = prof;
   }
   if (launch_search_proj(P, d_kps, d_desc, d_n, d_uright, d_blocked, d_mps, d_mpdesc, d_nmp, frames, d_out,
                          d_nmatches, stream))
-    return mfail(ORBX_EDEVICE, "search_proj launch: %s", hipGetErrorString(hipGetLastError()));
+    return g_merr.fail(ORBX_EDEVICE, "search_proj launch: %s", hipGetErrorString(hipGetLastError()));
   if (do_prof) {
     long long h[64];
-    MHIP(hipStreamSynchronize((hipStream_t)stream));
-    MHIP(hipMemcpy(h, prof, sizeof h, hipMemcpyDeviceToHost));
+    HIP_OK(g_merr, hipStreamSynchronize((hipStream_t)stream));
+    HIP_OK(g_merr, hipMemcpy(h, prof, sizeof h, hipMemcpyDeviceToHost));
     fprintf(stderr, "proj prof frame 0:");
     for (int i = 1; i < 42 && h[i]; ++i) fprintf(stderr, " r%d=%lld", i - 1, h[i] - h[0]);
     fprintf(stderr, "\n");
@@ -799,9 +759,9 @@ int orbm_search_by_projection(orbm_handle m, const orbx_kp* kps, const uint8_t* 
                               float nnratio, int* out, int* nmatches) {
   if (!m || !nmatches || n < 0 || nmp < 0 || (n && (!kps || !desc || !blocked || !out)) ||
       (nmp && (!mps || !mpdesc)))
-    return mfail(ORBX_EINVAL, "bad argument");
-  if (nmp > 8192) return mfail(ORBX_ECAPACITY, "more than 8192 map points");
-  MHIP(hipSetDevice(m->device));
+    return g_merr.fail(ORBX_EINVAL, "bad argument");
+  if (nmp > 8192) return g_merr.fail(ORBX_ECAPACITY, "more than 8192 map points");
+  HIP_OK(g_merr, hipSetDevice(m->device));
   const int kp = std::max(n, 1), mp = std::max(nmp, 1);
   const int hn[2] = {n, nmp};
   int nm = 0, rc;
@@ -829,8 +789,8 @@ int orbm_search_by_projection(orbm_handle m, const orbx_kp* kps, const uint8_t* 
 // ------------------------------- Frame::isInFrustum, Tracking::SearchLocalPoints
 static int frustum_params(orbm_grid_bounds b, float scale_factor, int nlevels, float viewing_cos_limit, int mp_pitch,
                           FrustumParams* P) {
-  if (nlevels < 1 || nlevels > kMaxLevels) return mfail(ORBX_EINVAL, "nlevels must be in 1..%d", kMaxLevels);
-  if (!(b.max_x > b.min_x) || !(b.max_y > b.min_y)) return mfail(ORBX_EINVAL, "empty grid bounds");
+  if (nlevels < 1 || nlevels > kMaxLevels) return g_merr.fail(ORBX_EINVAL, "nlevels must be in 1..%d", kMaxLevels);
+  if (!(b.max_x > b.min_x) || !(b.max_y > b.min_y)) return g_merr.fail(ORBX_EINVAL, "empty grid bounds");
   *P = FrustumParams{};
   P->minX = b.min_x;
   P->maxX = b.max_x;
@@ -861,7 +821,7 @@ static int frustum_params(orbm_grid_bounds b, float scale_factor, int nlevels, f
 int orbm_is_in_frustum(const orbm_pose* pose, orbm_grid_bounds b, float scale_factor, int nlevels,
                        float viewing_cos_limit, const orbm_map_point_world* mps, int nmp, orbm_map_point_proj* out,
                        int* n_in_view) {
-  if (!pose || !n_in_view || nmp < 0 || (nmp && (!mps || !out))) return mfail(ORBX_EINVAL, "bad argument");
+  if (!pose || !n_in_view || nmp < 0 || (nmp && (!mps || !out))) return g_merr.fail(ORBX_EINVAL, "bad argument");
   FrustumParams P;
   const int rc = frustum_params(b, scale_factor, nlevels, viewing_cos_limit, std::max(nmp, 1), &P);
   if (rc) return rc;
@@ -876,15 +836,15 @@ int orbm_is_in_frustum_batch(orbm_handle m, const orbm_pose* d_poses, orbm_grid_
                              const int* d_nmp, int mp_pitch, int frames, orbm_map_point_proj* d_out,
                              int* d_n_in_view, void* stream) {
   if (!m || !d_poses || !d_mps || !d_nmp || !d_out || !d_n_in_view || frames < 1 || mp_pitch < 1)
-    return mfail(ORBX_EINVAL, "bad argument");
-  if (mp_pitch > 65536) return mfail(ORBX_ECAPACITY, "more than 65536 map points per frame");
+    return g_merr.fail(ORBX_EINVAL, "bad argument");
+  if (mp_pitch > 65536) return g_merr.fail(ORBX_ECAPACITY, "more than 65536 map points per frame");
   FrustumParams P;
   const int rc = frustum_params(b, scale_factor, nlevels, viewing_cos_limit, mp_pitch, &P);
   if (rc) return rc;
-  MHIP(hipSetDevice(m->device));
-  MHIP(hipMemsetAsync(d_n_in_view, 0, (size_t)frames * 4, (hipStream_t)stream));
+  HIP_OK(g_merr, hipSetDevice(m->device));
+  HIP_OK(g_merr, hipMemsetAsync(d_n_in_view, 0, (size_t)frames * 4, (hipStream_t)stream));
   if (launch_frustum(P, d_poses, d_mps, d_nmp, frames, d_out, d_n_in_view, stream))
-    return mfail(ORBX_EDEVICE, "frustum launch: %s", hipGetErrorString(hipGetLastError()));
+    return g_merr.fail(ORBX_EDEVICE, "frustum launch: %s", hipGetErrorString(hipGetLastError()));
   return ORBX_OK;
 }
 
@@ -900,13 +860,13 @@ static int local_points_batch(orbm_handle m, const orbx_kp* d_kps, const uint8_t
                               bool status) {
   if (!m || !d_kps || !d_desc || !d_n || !scale || !d_blocked || !d_poses || !d_mps || !d_mpdesc || !d_nmp ||
       !d_out || !d_nmatches || !d_n_in_view || frames < 1 || kp_pitch < 1 || mp_pitch < 1)
-    return mfail(ORBX_EINVAL, "bad argument");
-  if (mp_pitch > 65536) return mfail(ORBX_ECAPACITY, "more than 65536 map points per frame");
-  if (proj_lds_bytes(kp_pitch) > 156 * 1024) return mfail(ORBX_ECAPACITY, "kp_pitch %d too large", kp_pitch);
+    return g_merr.fail(ORBX_EINVAL, "bad argument");
+  if (mp_pitch > 65536) return g_merr.fail(ORBX_ECAPACITY, "more than 65536 map points per frame");
+  if (proj_lds_bytes(kp_pitch) > 156 * 1024) return g_merr.fail(ORBX_ECAPACITY, "kp_pitch %d too large", kp_pitch);
   FrustumParams P;
   int rc = frustum_params(b, scale_factor, nlevels, viewing_cos_limit, mp_pitch, &P);
   if (rc) return rc;
-  MHIP(hipSetDevice(m->device));
+  HIP_OK(g_merr, hipSetDevice(m->device));
   hipStream_t s = (hipStream_t)stream;
   // scratch: the isInFrustum records (when the caller keeps none), then per
   // frame the points in view: records, descriptors, original indices, count
@@ -917,33 +877,30 @@ static int local_points_batch(orbm_handle m, const orbx_kp* d_kps, const uint8_t
   const size_t o_cmap = o_cdesc + a256((size_t)frames * cp * 32);
   const size_t o_cnmp = o_cmap + a256((size_t)frames * cp * 4);
   const size_t need = o_cnmp + a256((size_t)frames * 4);
-  if (m->ws.before(s)) return mfail(ORBX_EDEVICE, "stream wait on the workspace failed");
-  if (m->view_ws_bytes < need) {
-    if (m->ws.ev) MHIP(hipEventSynchronize(m->ws.ev));
-    if (m->view_ws) MHIP(hipFree(m->view_ws));
-    m->view_ws = nullptr;
-    m->view_ws_bytes = 0;
-    if (hipMalloc(&m->view_ws, need) != hipSuccess) return mfail(ORBX_ENOMEM, "local points workspace");
-    m->view_ws_bytes = need;
+  if (m->ws.before(s)) return g_merr.fail(ORBX_EDEVICE, "stream wait on the workspace failed");
+  if (m->view_ws.n < need) {
+    if (m->ws.ev) HIP_OK(g_merr, hipEventSynchronize(m->ws.ev));
+    if (m->view_ws.reserve(need) != hipSuccess) return g_merr.fail(ORBX_ENOMEM, "local points workspace");
   }
-  orbm_map_point_proj* proj = d_proj ? d_proj : (orbm_map_point_proj*)m->view_ws;
-  orbm_map_point_proj* c_proj = (orbm_map_point_proj*)(m->view_ws + o_cproj);
-  uint8_t* c_desc = m->view_ws + o_cdesc;
-  int* c_map = (int*)(m->view_ws + o_cmap);
-  int* c_nmp = (int*)(m->view_ws + o_cnmp);
-  MHIP(hipMemsetAsync(d_n_in_view, 0, (size_t)frames * 4, s));
+  uint8_t* ws = m->view_ws.as<uint8_t>();
+  orbm_map_point_proj* proj = d_proj ? d_proj : m->view_ws.as<orbm_map_point_proj>();
+  orbm_map_point_proj* c_proj = (orbm_map_point_proj*)(ws + o_cproj);
+  uint8_t* c_desc = ws + o_cdesc;
+  int* c_map = (int*)(ws + o_cmap);
+  int* c_nmp = (int*)(ws + o_cnmp);
+  HIP_OK(g_merr, hipMemsetAsync(d_n_in_view, 0, (size_t)frames * 4, s));
   if (launch_frustum(P, d_poses, d_mps, d_nmp, frames, proj, d_n_in_view, stream) ||
       launch_compact_in_view(proj, d_mpdesc, d_nmp, mp_pitch, frames, c_proj, c_desc, c_map, c_nmp, cp,
-                             status ? m->err : nullptr, stream))
-    return mfail(ORBX_EDEVICE, "local points launch: %s", hipGetErrorString(hipGetLastError()));
+                             status ? m->err.as<int>() : nullptr, stream))
+    return g_merr.fail(ORBX_EDEVICE, "local points launch: %s", hipGetErrorString(hipGetLastError()));
   // a frame with nothing in view (src/Tracking.cc:1268 skips the search) leaves out = -1, nmatches = 0
   if ((rc = orbm_search_by_projection_batch(m, d_kps, d_desc, d_n, kp_pitch, d_uright, b, scale, nlevels, d_blocked,
                                             c_proj, c_desc, c_nmp, cp, frames, th, nnratio, d_out, d_nmatches,
                                             stream)))
     return rc;
   if (launch_remap_out(d_out, d_n, kp_pitch, c_map, cp, frames, stream))
-    return mfail(ORBX_EDEVICE, "local points launch: %s", hipGetErrorString(hipGetLastError()));
-  if (m->ws.after(s) || (status && m->errm.mark(s))) return mfail(ORBX_EDEVICE, "event record failed");
+    return g_merr.fail(ORBX_EDEVICE, "local points launch: %s", hipGetErrorString(hipGetLastError()));
+  if (m->ws.after(s) || (status && m->errm.mark(s))) return g_merr.fail(ORBX_EDEVICE, "event record failed");
   return ORBX_OK;
 }
 
@@ -966,12 +923,12 @@ int orbm_search_local_points(orbm_handle m, const orbx_kp* kps, const uint8_t* d
                              int* out, int* nmatches, orbm_map_point_proj* proj, int* n_in_view) {
   if (!m || !nmatches || !n_in_view || !cur || !scale || n < 0 || nmp < 0 ||
       (n && (!kps || !desc || !blocked || !out)) || (nmp && (!mps || !mpdesc)))
-    return mfail(ORBX_EINVAL, "bad argument");
-  if (nmp > 65536) return mfail(ORBX_ECAPACITY, "more than 65536 map points");
+    return g_merr.fail(ORBX_EINVAL, "bad argument");
+  if (nmp > 65536) return g_merr.fail(ORBX_ECAPACITY, "more than 65536 map points");
   orbm_pose pose;
   int rc = orbm_prepare_pose(ORBM_PROJ_KEYFRAME, cur, nullptr, 0, &pose);
   if (rc) return rc;
-  MHIP(hipSetDevice(m->device));
+  HIP_OK(g_merr, hipSetDevice(m->device));
   const int kp = std::max(n, 1), mp = std::max(nmp, 1);
   const int hn[2] = {n, nmp};
   int nm = 0, niv = 0;
@@ -999,14 +956,14 @@ int orbm_search_local_points(orbm_handle m, const orbx_kp* kps, const uint8_t* d
     return rc;
   *n_in_view = niv;
   if (niv > kFrustumMaxView)
-    return mfail(ORBX_ECAPACITY, "%d map points in view, more than %d can be searched", niv, kFrustumMaxView);
+    return g_merr.fail(ORBX_ECAPACITY, "%d map points in view, more than %d can be searched", niv, kFrustumMaxView);
   *nmatches = nm;
   return ORBX_OK;
 }
 
 // ------------- MapPoint::ComputeDistinctiveDescriptors, UpdateNormalAndDepth
 int orbm_distinctive_descriptor(const uint8_t* desc, int n, int* best, int* median) {
-  if (!best || n < 0 || (n && !desc)) return mfail(ORBX_EINVAL, "bad argument");
+  if (!best || n < 0 || (n && !desc)) return g_merr.fail(ORBX_EINVAL, "bad argument");
   int best_i = -1, best_med = INT_MAX;
   std::vector<uint32_t> w((size_t)n * 8);
   if (n) memcpy(w.data(), desc, (size_t)n * 32);
@@ -1029,7 +986,7 @@ int orbm_distinctive_descriptor(const uint8_t* desc, int n, int* best, int* medi
 int orbm_update_normal_and_depth(const float* pos, const float* Ow_list, int n, const float* Ow_ref, float ref_scale,
                                  float last_scale, float* normal_out, float* min_distance, float* max_distance) {
   if (!pos || !Ow_ref || !normal_out || !min_distance || !max_distance || n < 0 || (n && !Ow_list))
-    return mfail(ORBX_EINVAL, "bad argument");
+    return g_merr.fail(ORBX_EINVAL, "bad argument");
   if (n == 0) return ORBX_OK;  // observations.empty() (src/MapPoint.cc:350)
   float sum[3] = {0.f, 0.f, 0.f}, t[3], out[5];
   for (int k = 0; k < n; ++k) {
@@ -1051,22 +1008,18 @@ int orbm_refresh_map_points_batch(orbm_handle m, const orbm_observation* d_obs, 
                                   const float* scale, int nlevels, orbm_map_point_world* d_mps, uint8_t* d_mpdesc,
                                   int* d_best, int* d_median, void* stream) {
   if (!m || !d_obs || !d_obs_off || !d_kfs || !d_desc || points < 1 || n_kfs < 0)
-    return mfail(ORBX_EINVAL, "bad argument");
-  if (!d_mps && !d_mpdesc && !d_best && !d_median) return mfail(ORBX_EINVAL, "nothing to refresh: no output array");
+    return g_merr.fail(ORBX_EINVAL, "bad argument");
+  if (!d_mps && !d_mpdesc && !d_best && !d_median) return g_merr.fail(ORBX_EINVAL, "nothing to refresh: no output array");
   if (d_mps && (!d_ref || !scale || nlevels < 1 || nlevels > kMaxLevels))
-    return mfail(ORBX_EINVAL, "records need d_ref and 1..%d scale factors", kMaxLevels);
-  if (((uintptr_t)d_desc | (uintptr_t)d_mpdesc) & 15) return mfail(ORBX_EINVAL, "descriptors must be 16-byte aligned");
-  MHIP(hipSetDevice(m->device));
+    return g_merr.fail(ORBX_EINVAL, "records need d_ref and 1..%d scale factors", kMaxLevels);
+  if (((uintptr_t)d_desc | (uintptr_t)d_mpdesc) & 15) return g_merr.fail(ORBX_EINVAL, "descriptors must be 16-byte aligned");
+  HIP_OK(g_merr, hipSetDevice(m->device));
   hipStream_t s = (hipStream_t)stream;
-  if (m->ws.before(s)) return mfail(ORBX_EDEVICE, "stream wait on the workspace failed");
+  if (m->ws.before(s)) return g_merr.fail(ORBX_EDEVICE, "stream wait on the workspace failed");
   const size_t need = refresh_ws_bytes(points);
-  if (m->refresh_ws_bytes < need) {
-    if (m->ws.ev) MHIP(hipEventSynchronize(m->ws.ev));
-    if (m->refresh_ws) MHIP(hipFree(m->refresh_ws));
-    m->refresh_ws = nullptr;
-    m->refresh_ws_bytes = 0;
-    if (hipMalloc(&m->refresh_ws, need) != hipSuccess) return mfail(ORBX_ENOMEM, "map point refresh workspace");
-    m->refresh_ws_bytes = need;
+  if (m->refresh_ws.n < need) {
+    if (m->ws.ev) HIP_OK(g_merr, hipEventSynchronize(m->ws.ev));
+    if (m->refresh_ws.reserve(need) != hipSuccess) return g_merr.fail(ORBX_ENOMEM, "map point refresh workspace");
   }
   RefreshArgs A{};
   A.obs = d_obs;
@@ -1084,12 +1037,12 @@ int orbm_refresh_map_points_batch(orbm_handle m, const orbm_observation* d_obs, 
   A.mpdesc = d_mpdesc;
   A.best = d_best;
   A.median = d_median;
-  A.err = m->err;
-  A.counts = (int*)m->refresh_ws;
-  A.lists = (int*)(m->refresh_ws + 256);
+  A.err = m->err.as<int>();
+  A.counts = m->refresh_ws.as<int>();
+  A.lists = (int*)(m->refresh_ws.as<uint8_t>() + 256);
   if (launch_refresh_map_points(A, stream))
-    return mfail(ORBX_EDEVICE, "map point refresh launch: %s", hipGetErrorString(hipGetLastError()));
-  if (m->ws.after(s) || m->errm.mark(s)) return mfail(ORBX_EDEVICE, "event record failed");
+    return g_merr.fail(ORBX_EDEVICE, "map point refresh launch: %s", hipGetErrorString(hipGetLastError()));
+  if (m->ws.after(s) || m->errm.mark(s)) return g_merr.fail(ORBX_EDEVICE, "event record failed");
   return ORBX_OK;
 }
 
@@ -1098,19 +1051,19 @@ int orbm_refresh_map_points(orbm_handle m, const orbm_observation* obs, const ui
                             const uint8_t* desc, uint32_t desc_rows, const orbm_point_refkf* ref, const float* scale,
                             int nlevels, orbm_map_point_world* mps, uint8_t* mpdesc, int n_mps, int* best,
                             int* median) {
-  if (!m || !obs_off || points < 0 || n_kfs < 0 || n_mps < 0) return mfail(ORBX_EINVAL, "bad argument");
+  if (!m || !obs_off || points < 0 || n_kfs < 0 || n_mps < 0) return g_merr.fail(ORBX_EINVAL, "bad argument");
   if (points == 0) return ORBX_OK;
-  if (!mps && !mpdesc && !best && !median) return mfail(ORBX_EINVAL, "nothing to refresh: no output array");
+  if (!mps && !mpdesc && !best && !median) return g_merr.fail(ORBX_EINVAL, "nothing to refresh: no output array");
   for (int p = 0; p < points; ++p)
-    if (obs_off[p + 1] < obs_off[p]) return mfail(ORBX_EINVAL, "obs_off descends at point %d", p);
+    if (obs_off[p + 1] < obs_off[p]) return g_merr.fail(ORBX_EINVAL, "obs_off descends at point %d", p);
   const size_t nobs = obs_off[points];
-  if (nobs && (!obs || !kfs || !desc || !n_kfs || !desc_rows)) return mfail(ORBX_EINVAL, "null array");
+  if (nobs && (!obs || !kfs || !desc || !n_kfs || !desc_rows)) return g_merr.fail(ORBX_EINVAL, "null array");
   if (mps || mpdesc) {
-    if (!point_ids && n_mps < points) return mfail(ORBX_EINVAL, "%d points in a table of %d", points, n_mps);
+    if (!point_ids && n_mps < points) return g_merr.fail(ORBX_EINVAL, "%d points in a table of %d", points, n_mps);
     for (int p = 0; point_ids && p < points; ++p)
-      if (point_ids[p] >= (uint32_t)n_mps) return mfail(ORBX_EINVAL, "point id %u outside the table", point_ids[p]);
+      if (point_ids[p] >= (uint32_t)n_mps) return g_merr.fail(ORBX_EINVAL, "point id %u outside the table", point_ids[p]);
   }
-  MHIP(hipSetDevice(m->device));
+  HIP_OK(g_merr, hipSetDevice(m->device));
   const size_t tab = std::max(n_mps, 1), nk = std::max(n_kfs, 1), nr = std::max<size_t>(desc_rows, 1);
   int rc;
   Stage st(m);
@@ -1178,7 +1131,7 @@ int orbm_pose_optimization_host(const orbx_kp* kps, int n, const float* uright, 
                                 orbm_poseopt_result* result, int* status) {
   if (n < 0 || nmp < 0 || !cam || !inv_sigma2 || nlevels < 1 || nlevels > kMaxLevels || (n && (!kps || !assign)) ||
       (nmp && !mps))
-    return mfail(ORBX_EINVAL, "bad argument");
+    return g_merr.fail(ORBX_EINVAL, "bad argument");
   // an edge's tag holds the keypoint index in 16 bits; the index travels beside it here
   std::vector<PoEdge> E;
   std::vector<int> index;
@@ -1243,20 +1196,16 @@ int orbm_pose_optimization_batch(orbm_handle m, const orbx_kp* d_kps, const int*
                                  uint8_t* d_outlier, orbm_poseopt_result* d_result, void* stream) {
   if (!m || !d_kps || !d_n || !d_assign || !d_mps || !d_nmp || !inv_sigma2 || !d_cams || frames < 1 || kp_pitch < 1 ||
       mp_pitch < 1 || nlevels < 1 || nlevels > kMaxLevels)
-    return mfail(ORBX_EINVAL, "bad argument");
-  if (kp_pitch > m->max_kps) return mfail(ORBX_ECAPACITY, "kp_pitch %d above the handle's max_kps %d", kp_pitch, m->max_kps);
-  MHIP(hipSetDevice(m->device));
+    return g_merr.fail(ORBX_EINVAL, "bad argument");
+  if (kp_pitch > m->max_kps) return g_merr.fail(ORBX_ECAPACITY, "kp_pitch %d above the handle's max_kps %d", kp_pitch, m->max_kps);
+  HIP_OK(g_merr, hipSetDevice(m->device));
   hipStream_t s = (hipStream_t)stream;
   const size_t need = poseopt_spill_bytes(kp_pitch, frames);
   if (need) {
-    if (m->ws.before(s)) return mfail(ORBX_EDEVICE, "stream wait on the workspace failed");
-    if (m->po_ws_bytes < need) {
-      if (m->ws.ev) MHIP(hipEventSynchronize(m->ws.ev));
-      if (m->po_ws) MHIP(hipFree(m->po_ws));
-      m->po_ws = nullptr;
-      m->po_ws_bytes = 0;
-      if (hipMalloc(&m->po_ws, need) != hipSuccess) return mfail(ORBX_ENOMEM, "pose optimisation workspace");
-      m->po_ws_bytes = need;
+    if (m->ws.before(s)) return g_merr.fail(ORBX_EDEVICE, "stream wait on the workspace failed");
+    if (m->po_ws.n < need) {
+      if (m->ws.ev) HIP_OK(g_merr, hipEventSynchronize(m->ws.ev));
+      if (m->po_ws.reserve(need) != hipSuccess) return g_merr.fail(ORBX_ENOMEM, "pose optimisation workspace");
     }
   }
   PoseOptArgs A{};
@@ -1277,10 +1226,10 @@ int orbm_pose_optimization_batch(orbm_handle m, const orbx_kp* d_kps, const int*
   A.pose = d_pose;
   A.outlier = d_outlier;
   A.result = d_result;
-  A.err = m->err;
-  if (launch_pose_optimization(A, need ? m->po_ws : nullptr, stream))
-    return mfail(ORBX_EDEVICE, "pose optimisation launch: %s", hipGetErrorString(hipGetLastError()));
-  if ((need && m->ws.after(s)) || m->errm.mark(s)) return mfail(ORBX_EDEVICE, "event record failed");
+  A.err = m->err.as<int>();
+  if (launch_pose_optimization(A, need ? m->po_ws.p : nullptr, stream))
+    return g_merr.fail(ORBX_EDEVICE, "pose optimisation launch: %s", hipGetErrorString(hipGetLastError()));
+  if ((need && m->ws.after(s)) || m->errm.mark(s)) return g_merr.fail(ORBX_EDEVICE, "event record failed");
   return ORBX_OK;
 }
 
@@ -1289,9 +1238,9 @@ int orbm_pose_optimization(orbm_handle m, const orbx_kp* kps, int n, const float
                            const orbm_camera* cam, int flags, float* Tcw, orbm_pose* pose, uint8_t* outlier,
                            orbm_poseopt_result* result) {
   if (!m || n < 0 || nmp < 0 || !cam || (n && (!kps || !assign)) || (nmp && !mps))
-    return mfail(ORBX_EINVAL, "bad argument");
-  if (n > m->max_kps) return mfail(ORBX_ECAPACITY, "%d keypoints above the handle's max_kps %d", n, m->max_kps);
-  MHIP(hipSetDevice(m->device));
+    return g_merr.fail(ORBX_EINVAL, "bad argument");
+  if (n > m->max_kps) return g_merr.fail(ORBX_ECAPACITY, "%d keypoints above the handle's max_kps %d", n, m->max_kps);
+  HIP_OK(g_merr, hipSetDevice(m->device));
   const size_t kp = std::max(n, 1), np = std::max(nmp, 1);
   int rc;
   Stage st(m);
@@ -1342,7 +1291,7 @@ int host_predict_direct(float ratio, float logsf, int L) {
 int orbm_prepare_pose(int mode, const orbm_camera* cam, const float* Tlw, int mono, orbm_pose* out) {
   if (!cam || !out || mode < ORBM_PROJ_LAST_FRAME || mode > ORBM_PROJ_FUSE_SIM3 ||
       (mode == ORBM_PROJ_LAST_FRAME && !Tlw))
-    return mfail(ORBX_EINVAL, "bad argument");
+    return g_merr.fail(ORBX_EINVAL, "bad argument");
   float Rt[12];
   if (mode == ORBM_PROJ_SIM3 || mode == ORBM_PROJ_FUSE_SIM3) {
     // scw = sqrt(sRcw.row(0).dot(sRcw.row(0))); Rcw = sRcw/scw; tcw = t/scw
@@ -1350,7 +1299,7 @@ int orbm_prepare_pose(int mode, const orbm_camera* cam, const float* Tlw, int mo
     const float* S = cam->Tcw;
     const double d = (double)S[0] * S[0] + (double)S[1] * S[1] + (double)S[2] * S[2];
     const float scw = (float)std::sqrt(d);
-    if (!(scw > 0)) return mfail(ORBX_EINVAL, "Scw has a zero scale");
+    if (!(scw > 0)) return g_merr.fail(ORBX_EINVAL, "Scw has a zero scale");
     const float a = (float)(1.0 / (double)scw);
     for (int k = 0; k < 12; ++k) Rt[k] = S[k] * a + 0.0f;
   } else {
@@ -1372,7 +1321,7 @@ int orbm_prepare_pose(int mode, const orbm_camera* cam, const float* Tlw, int mo
 
 int orbm_prepare_sim3_match(const orbm_camera* cam1, const float* T1w, const float* T2w, float s12, const float* R12,
                             const float* t12, orbm_pose* out) {
-  if (!cam1 || !T1w || !T2w || !R12 || !t12 || !out || !(s12 != 0.0f)) return mfail(ORBX_EINVAL, "bad argument");
+  if (!cam1 || !T1w || !T2w || !R12 || !t12 || !out || !(s12 != 0.0f)) return g_merr.fail(ORBX_EINVAL, "bad argument");
   // sR12 = s12*R12; sR21 = (1.0/s12)*R12.t(); t21 = -sR21*t12 (src/ORBmatcher.cc:1118-1120):
   // scalar * Mat = convertTo(alpha) in float, -A*t = gemm small path with alpha -1
   const float a12 = (float)(double)s12, a21 = (float)(1.0 / (double)s12);
@@ -1404,7 +1353,7 @@ int orbm_prepare_sim3_match(const orbm_camera* cam1, const float* T1w, const flo
 
 int orbm_predict_scale_thresholds(float scale_factor, int nlevels, float* thr) {
   if (!thr || nlevels < 1 || nlevels > kMaxLevels || !(scale_factor > 1.0f))
-    return mfail(ORBX_EINVAL, "bad argument");
+    return g_merr.fail(ORBX_EINVAL, "bad argument");
   const float logsf = std::log(scale_factor);  // Frame::mfLogScaleFactor (src/Frame.cc:70)
   for (int k = 1; k < nlevels; ++k) {
     // least positive float r with level(r) >= k; level is non-decreasing in r
@@ -1414,7 +1363,7 @@ int orbm_predict_scale_thresholds(float scale_factor, int nlevels, float* thr) {
       std::memcpy(&f, &b, 4);
       return f;
     };
-    if (host_predict_direct(at(hi), logsf, nlevels) < k) return mfail(ORBX_EINVAL, "scale factor too small");
+    if (host_predict_direct(at(hi), logsf, nlevels) < k) return g_merr.fail(ORBX_EINVAL, "scale factor too small");
     while (hi - lo > 1) {
       const uint32_t mid = lo + (hi - lo) / 2;
       if (host_predict_direct(at(mid), logsf, nlevels) >= k)
@@ -1450,10 +1399,10 @@ int orbm_search_by_projection_pose_batch(orbm_handle m, int mode, const orbx_kp*
       !d_out || !d_nmatches || frames < 1 || kp_pitch < 1 || mp_pitch < 1 || nlevels < 1 ||
       nlevels > kMaxLevels || mode < ORBM_PROJ_LAST_FRAME || mode > ORBM_PROJ_SIM3_MATCH ||
       (mode == ORBM_PROJ_FUSE && !inv_sigma2))
-    return mfail(ORBX_EINVAL, "bad argument");
-  if (!(b.max_x > b.min_x) || !(b.max_y > b.min_y)) return mfail(ORBX_EINVAL, "empty grid bounds");
-  if (pose_lds_bytes(kp_pitch) > 156 * 1024) return mfail(ORBX_ECAPACITY, "kp_pitch %d too large", kp_pitch);
-  MHIP(hipSetDevice(m->device));
+    return g_merr.fail(ORBX_EINVAL, "bad argument");
+  if (!(b.max_x > b.min_x) || !(b.max_y > b.min_y)) return g_merr.fail(ORBX_EINVAL, "empty grid bounds");
+  if (pose_lds_bytes(kp_pitch) > 156 * 1024) return g_merr.fail(ORBX_ECAPACITY, "kp_pitch %d too large", kp_pitch);
+  HIP_OK(g_merr, hipSetDevice(m->device));
   PoseParams P{};
   P.mode = mode;
   set_grid_bounds(P, b);
@@ -1472,20 +1421,16 @@ int orbm_search_by_projection_pose_batch(orbm_handle m, int mode, const orbx_kp*
   for (int l = 0; l < kMaxLevels; ++l) P.inv_sigma2[l] = inv_sigma2 ? inv_sigma2[std::min(l, nlevels - 1)] : 0.f;
   P.max_rounds = 32;
   if (const char* e = getenv("ORBX_PROJ_ROUNDS")) P.max_rounds = atoi(e);  // tests: force the sequential pass
-  const size_t need = (size_t)frames * mp_pitch;
-  if (m->ws.before((hipStream_t)stream)) return mfail(ORBX_EDEVICE, "stream wait on the workspace failed");
-  if (m->pose_picks_cap < need) {
-    if (m->ws.ev) MHIP(hipEventSynchronize(m->ws.ev));
-    if (m->pose_picks) MHIP(hipFree(m->pose_picks));
-    m->pose_picks = nullptr;
-    m->pose_picks_cap = 0;
-    if (hipMalloc(&m->pose_picks, need * 4) != hipSuccess) return mfail(ORBX_ENOMEM, "pose picks workspace");
-    m->pose_picks_cap = need;
+  const size_t need = (size_t)frames * mp_pitch * 4;
+  if (m->ws.before((hipStream_t)stream)) return g_merr.fail(ORBX_EDEVICE, "stream wait on the workspace failed");
+  if (m->pose_picks.n < need) {
+    if (m->ws.ev) HIP_OK(g_merr, hipEventSynchronize(m->ws.ev));
+    if (m->pose_picks.reserve(need) != hipSuccess) return g_merr.fail(ORBX_ENOMEM, "pose picks workspace");
   }
   if (launch_search_pose(P, d_kps, d_desc, d_n, d_uright, d_blocked, d_poses, d_mps, d_mpdesc, d_nmp, frames,
-                         m->pose_picks, d_out, d_nmatches, stream))
-    return mfail(ORBX_EDEVICE, "search_pose launch: %s", hipGetErrorString(hipGetLastError()));
-  if (m->ws.after((hipStream_t)stream)) return mfail(ORBX_EDEVICE, "event record failed");
+                         m->pose_picks.as<int>(), d_out, d_nmatches, stream))
+    return g_merr.fail(ORBX_EDEVICE, "search_pose launch: %s", hipGetErrorString(hipGetLastError()));
+  if (m->ws.after((hipStream_t)stream)) return g_merr.fail(ORBX_EDEVICE, "event record failed");
   return ORBX_OK;
 }
 
@@ -1498,8 +1443,8 @@ int pose_sync(orbm_handle m, int mode, const orbx_kp* kps, const uint8_t* desc, 
   const bool pp = mode == ORBM_PROJ_FUSE || mode == ORBM_PROJ_FUSE_SIM3 || mode == ORBM_PROJ_SIM3_MATCH;
   if (!m || !nmatches || n < 0 || nmp < 0 || (n && (!kps || !desc)) || (nmp && (!mps || !mpdesc)) ||
       ((pp ? nmp : n) && !out))
-    return mfail(ORBX_EINVAL, "bad argument");
-  MHIP(hipSetDevice(m->device));
+    return g_merr.fail(ORBX_EINVAL, "bad argument");
+  HIP_OK(g_merr, hipSetDevice(m->device));
   const int kp = std::max(n, 1), mp = std::max(nmp, 1);
   std::vector<uint8_t> bl(kp, 0);  // a null `blocked` uploads zeros
   if (blocked && n) std::memcpy(bl.data(), blocked, n);
@@ -1570,7 +1515,7 @@ int orbm_search_by_projection_sim3(orbm_handle m, const orbx_kp* kps, const uint
 int orbm_fuse(orbm_handle m, const orbx_kp* kps, const uint8_t* desc, int n, const float* uright, orbm_grid_bounds b,
               const float* scale, const float* inv_sigma2, int nlevels, float scale_factor, const orbm_camera* kf,
               const orbm_map_point_world* mps, const uint8_t* mpdesc, int nmp, float th, int* out, int* nfused) {
-  if (!inv_sigma2) return mfail(ORBX_EINVAL, "bad argument");
+  if (!inv_sigma2) return g_merr.fail(ORBX_EINVAL, "bad argument");
   orbm_pose pose;
   int rc = orbm_prepare_pose(ORBM_PROJ_FUSE, kf, nullptr, 0, &pose);
   if (rc) return rc;
@@ -1594,7 +1539,7 @@ int orbm_search_by_sim3(orbm_handle m, const orbx_kp* kps1, const uint8_t* desc1
                         const orbm_map_point_world* mps2, const uint8_t* mpdesc2, const float* scale, int nlevels,
                         float scale_factor, const orbm_camera* cam1, float s12, const float* R12, const float* t12,
                         float th, int* match12, int* nfound) {
-  if (!nfound || n1 < 0 || n2 < 0 || (n1 && !match12)) return mfail(ORBX_EINVAL, "bad argument");
+  if (!nfound || n1 < 0 || n2 < 0 || (n1 && !match12)) return g_merr.fail(ORBX_EINVAL, "bad argument");
   orbm_pose pz[2];
   int rc = orbm_prepare_sim3_match(cam1, T1w, T2w, s12, R12, t12, pz);
   if (rc) return rc;
@@ -1623,7 +1568,7 @@ int orbm_search_by_sim3(orbm_handle m, const orbx_kp* kps1, const uint8_t* desc1
 
 int orbm_prepare_triangulation(const float* cw1, const float* T2w, const float* cam2, const float* F12,
                                orbm_tri_pair* out) {
-  if (!cw1 || !T2w || !cam2 || !F12 || !out) return mfail(ORBX_EINVAL, "bad argument");
+  if (!cw1 || !T2w || !cam2 || !F12 || !out) return g_merr.fail(ORBX_EINVAL, "bad argument");
   // C2 = R2w*Cw + t2w; invz = 1.0f/C2.z; ex = fx*C2.x*invz + cx (src/ORBmatcher.cc:664-670)
   float C2[3];
   host_rx_t(T2w, cw1, C2);
@@ -1648,8 +1593,8 @@ int orbm_search_for_triangulation_batch(
       !d_pairs || !scale2 || !sigma2 || !d_matches12 || !d_nmatches || pairs < 1 || nlevels < 1 ||
       nlevels > kMaxLevels || kp_pitch1 < 0 || node_pitch1 < 0 || kp_pitch2 < 1 || node_pitch2 < 1 || out_pitch < 1 ||
       ((kp_pitch1 == 0) != (node_pitch1 == 0)))
-    return mfail(ORBX_EINVAL, "bad argument");
-  MHIP(hipSetDevice(m->device));
+    return g_merr.fail(ORBX_EINVAL, "bad argument");
+  HIP_OK(g_merr, hipSetDevice(m->device));
   TriParams P{};
   for (int l = 0; l < kMaxLevels; ++l) {
     P.scale2[l] = scale2[std::min(l, nlevels - 1)];
@@ -1663,7 +1608,7 @@ int orbm_search_for_triangulation_batch(
   const TriSide B{d_kps2, d_desc2, d_uright2, d_has_mp2, d_n2, d_nodes2, d_off2, d_idx2, d_nn2, kp_pitch2,
                   node_pitch2};
   if (launch_search_tri(P, A, B, d_pairs, pairs, d_matches12, d_nmatches, stream))
-    return mfail(ORBX_EDEVICE, "search_tri launch: %s", hipGetErrorString(hipGetLastError()));
+    return g_merr.fail(ORBX_EDEVICE, "search_tri launch: %s", hipGetErrorString(hipGetLastError()));
   return ORBX_OK;
 }
 
@@ -1677,17 +1622,17 @@ int orbm_search_for_triangulation(orbm_handle m, const orbx_kp* kps1, const uint
       (n1 && (!kps1 || !desc1 || !uright1 || !has_mp1 || !matches12)) ||
       (n2 && (!kps2 || !desc2 || !uright2 || !has_mp2)) || (fv1.n_nodes && (!fv1.nodes || !fv1.off)) ||
       (fv2.n_nodes && (!fv2.nodes || !fv2.off)))
-    return mfail(ORBX_EINVAL, "bad argument");
+    return g_merr.fail(ORBX_EINVAL, "bad argument");
   orbm_tri_pair tp;
   int rc = orbm_prepare_triangulation(cw1, T2w, cam2, F12, &tp);
   if (rc) return rc;
   const int f1 = fv1.n_nodes ? fv1.off[fv1.n_nodes] : 0, f2 = fv2.n_nodes ? fv2.off[fv2.n_nodes] : 0;
-  if (f1 > n1 || f2 > n2) return mfail(ORBX_EINVAL, "feature vector holds more indices than keypoints");
+  if (f1 > n1 || f2 > n2) return g_merr.fail(ORBX_EINVAL, "feature vector holds more indices than keypoints");
   for (int i = 0; i < f1; ++i)
-    if (fv1.idx[i] < 0 || fv1.idx[i] >= n1) return mfail(ORBX_EINVAL, "feature index out of range");
+    if (fv1.idx[i] < 0 || fv1.idx[i] >= n1) return g_merr.fail(ORBX_EINVAL, "feature index out of range");
   for (int i = 0; i < f2; ++i)
-    if (fv2.idx[i] < 0 || fv2.idx[i] >= n2) return mfail(ORBX_EINVAL, "feature index out of range");
-  MHIP(hipSetDevice(m->device));
+    if (fv2.idx[i] < 0 || fv2.idx[i] >= n2) return g_merr.fail(ORBX_EINVAL, "feature index out of range");
+  HIP_OK(g_merr, hipSetDevice(m->device));
   const int k1 = std::max(n1, 1), k2 = std::max(n2, 1);
   const int nn1 = std::max(fv1.n_nodes, 1), nn2 = std::max(fv2.n_nodes, 1);
   const int zero = 0;  // an empty FeatureVector's off[0]

@@ -3,7 +3,7 @@
 // Level l = cv::resize(level l-1, size_l, INTER_LINEAR), chained. OpenCV 3.x
 // evaluates INTER_LINEAR on u8 in fixed point: 11-bit horizontal and vertical
 // coefficients (tables built on the host from the same float expressions,
-// orbx_host.hip resize_tables), an int32 horizontal pass, and the vertical
+// orbx_plan.hip resize_tables), an int32 horizontal pass, and the vertical
 // pass (D0*b0 + D1*b1 + 2^21) >> 22; columns at or beyond `xmax` replicate
 // the source pixel (x2048). An exact 2x downscale switches to the 2x2 area
 // mean, as cv::resize does. The 19-px border the reference pads each level
@@ -136,7 +136,7 @@ __global__ __launch_bounds__(256) void pyr_resize_kernel(
 // and columns it owns at each level (tiles partition every level; the few
 // source rows and columns two tiles share are recomputed by both instead of
 // exchanged). Ranges per (band, level) and (column tile, level) come from the
-// host (orbx_host.hip plan_band_pyramid / plan_pyr_cols): comp = computed,
+// host (orbx_plan.hip plan_band_pyramid / plan_pyr_cols): comp = computed,
 // own = written. Column tiles let a single frame (or a small batch) spread
 // over more workgroups than row bands alone allow, at a few recomputed
 // columns per tile edge.

@@ -32,6 +32,7 @@
 #include <cmath>
 
 #include "orbx_device.cuh"
+#include "orbx_hostutil.h"
 #include "orbx_remap.cuh"
 
 namespace orbx {
@@ -279,3 +280,71 @@ void rectify_maps_host(const double* K, const double* D, const double* R, const 
 }
 
 }  // namespace orbx
+
+// ------------------------------------------- C ABI (the rectifier's own entry points)
+using namespace orbx;
+
+static bool remap_side_ok(int v) { return v >= 1 && v <= 32766; }
+
+extern "C" {
+
+int orbx_rectify_maps(const double K[9], const double D[5], const double R[9], const double P[12], int w, int hh,
+                      float* map1, float* map2) {
+  if (!K || !D || !R || !P || !map1 || !map2) return g_err.fail(ORBX_EINVAL, "orbx_rectify_maps: null argument");
+  if (!remap_side_ok(w) || !remap_side_ok(hh))
+    return g_err.fail(ORBX_EINVAL, "orbx_rectify_maps: size %d x %d outside 1 .. 32766", w, hh);
+  rectify_maps_host(K, D, R, P, w, hh, map1, map2);
+  return ORBX_OK;
+}
+
+int orbx_remap_host(const uint8_t* src, int src_w, int src_h, size_t src_stride, const float* map1,
+                    const float* map2, int dst_w, int dst_h, uint8_t* dst, size_t dst_stride) {
+  if (!src || !map1 || !map2 || !dst) return g_err.fail(ORBX_EINVAL, "orbx_remap_host: null argument");
+  if (!remap_side_ok(src_w) || !remap_side_ok(src_h) || !remap_side_ok(dst_w) || !remap_side_ok(dst_h))
+    return g_err.fail(ORBX_EINVAL, "orbx_remap_host: %d x %d to %d x %d: a side outside 1 .. 32766", src_w, src_h, dst_w,
+                dst_h);
+  if (src_stride < (size_t)src_w || dst_stride < (size_t)dst_w)
+    return g_err.fail(ORBX_EINVAL, "orbx_remap_host: a row stride below its width");
+  remap_host(src, src_w, src_h, src_stride, map1, map2, dst_w, dst_h, dst, dst_stride);
+  return ORBX_OK;
+}
+
+int orbx_rectify_create(int device, const float* map1, const float* map2, int dst_w, int dst_h, int src_w,
+                        int src_h, orbx_rectify_handle* out) {
+  if (!map1 || !map2 || !out) return g_err.fail(ORBX_EINVAL, "orbx_rectify_create: null argument");
+  if (!remap_side_ok(src_w) || !remap_side_ok(src_h) || !remap_side_ok(dst_w) || !remap_side_ok(dst_h))
+    return g_err.fail(ORBX_EINVAL, "orbx_rectify_create: %d x %d to %d x %d: a side outside 1 .. 32766", src_w, src_h, dst_w,
+                dst_h);
+  const int rc = rectifier_create(device, map1, map2, dst_w, dst_h, src_w, src_h, out);
+  if (rc) return g_err.fail(rc, "orbx_rectify_create: %s", hipGetErrorString(hipGetLastError()));
+  return ORBX_OK;
+}
+
+int orbx_rectify_destroy(orbx_rectify_handle r) {
+  if (!r) return ORBX_OK;
+  (void)hipSetDevice(r->device);
+  rectifier_destroy(r);
+  return ORBX_OK;
+}
+
+int orbx_rectify_batch(orbx_rectify_handle r, const uint8_t* d_src, size_t src_stride, size_t src_frame_pitch,
+                       uint8_t* d_dst, size_t dst_stride, size_t dst_frame_pitch, int batch, void* stream) {
+  if (!r) return g_err.fail(ORBX_EINVAL, "orbx_rectify_batch: null rectifier");
+  if (batch < 0) return g_err.fail(ORBX_EINVAL, "orbx_rectify_batch: negative batch");
+  if (batch == 0) return ORBX_OK;
+  if (!d_src || !d_dst) return g_err.fail(ORBX_EINVAL, "orbx_rectify_batch: null image");
+  if (src_stride < (size_t)r->src_w || dst_stride < (size_t)r->dst_w)
+    return g_err.fail(ORBX_EINVAL, "orbx_rectify_batch: row strides %zu / %zu below the widths %d / %d", src_stride,
+                dst_stride, r->src_w, r->dst_w);
+  // the last row of a frame needs its width only
+  if (batch > 1 && (src_frame_pitch < src_stride * (size_t)(r->src_h - 1) + r->src_w ||
+                    dst_frame_pitch < dst_stride * (size_t)(r->dst_h - 1) + r->dst_w))
+    return g_err.fail(ORBX_EINVAL, "orbx_rectify_batch: a frame pitch below one frame");
+  HIP_OK(g_err, hipSetDevice(r->device));
+  if (launch_rectify(*r, d_src, src_stride, src_frame_pitch, d_dst, dst_stride, dst_frame_pitch, batch,
+                     (hipStream_t)stream))
+    return g_err.fail(ORBX_EDEVICE, "remap launch failed: %s", hipGetErrorString(hipGetLastError()));
+  return ORBX_OK;
+}
+
+}  // extern "C"

@@ -31,14 +31,13 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <string>
 #include <vector>
 
 #include "orbx_device.cuh"
+#include "orbx_hostutil.h"
 #include "orbx_internal.h"
 
 namespace orbx {
@@ -340,23 +339,8 @@ __global__ __launch_bounds__(kAsThreads) void voc_assemble_kernel(
 using namespace orbx;
 
 namespace {
-thread_local std::string g_verr;
-int vfail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  g_verr = buf;
-  return code;
-}
+thread_local ErrorSlot g_verr;  // the orbv_ family's last error
 }  // namespace
-
-#define VHIP(expr)                                                                             \
-  do {                                                                                         \
-    hipError_t e_ = (expr);                                                                    \
-    if (e_ != hipSuccess) return vfail(ORBX_EDEVICE, "%s: %s", #expr, hipGetErrorString(e_));  \
-  } while (0)
 
 struct orbv_vocabulary {
   int device = 0, k = 0, L = 0, scoring = 0, weighting = 0, n_nodes = 0, n_words = 0, max_children = 0;
@@ -366,31 +350,21 @@ struct orbv_vocabulary {
   double* weight = nullptr;
   uint32_t* orig = nullptr;
   // per-feature workspace and staging of the synchronous entry point
-  void* ws = nullptr;
-  size_t ws_bytes = 0;
+  DeviceBuf ws;
   hipStream_t stream = nullptr;
 };
 
-static int ws_reserve(orbv_vocabulary* v, size_t bytes) {
-  if (v->ws_bytes >= bytes) return ORBX_OK;
-  if (v->ws) (void)hipFree(v->ws);
-  v->ws = nullptr;
-  v->ws_bytes = 0;
-  VHIP(hipMalloc(&v->ws, bytes));
-  v->ws_bytes = bytes;
-  return ORBX_OK;
-}
-
 extern "C" {
 
-const char* orbv_last_error(void) { return g_verr.c_str(); }
+const char* orbv_last_error(void) { return g_verr.msg.c_str(); }
 
 int orbv_destroy(orbv_handle v) {
   if (!v) return ORBX_OK;
   (void)hipSetDevice(v->device);
   if (v->stream) (void)hipStreamSynchronize(v->stream);
-  for (void* p : {(void*)v->child, (void*)v->desc, (void*)v->word, (void*)v->weight, (void*)v->orig, v->ws})
+  for (void* p : {(void*)v->child, (void*)v->desc, (void*)v->word, (void*)v->weight, (void*)v->orig})
     if (p) (void)hipFree(p);
+  v->ws.release();
   if (v->stream) (void)hipStreamDestroy(v->stream);
   delete v;
   return ORBX_OK;
@@ -399,14 +373,14 @@ int orbv_destroy(orbv_handle v) {
 int orbv_create(int k, int L, int scoring, int weighting, int n_nodes, const int* parent, const uint8_t* is_leaf,
                 const uint8_t* desc, const double* weight, int device, orbv_handle* out) {
   if (!out || n_nodes < 1 || (n_nodes > 1 && (!parent || !is_leaf || !desc || !weight)))
-    return vfail(ORBX_EINVAL, "bad argument");
+    return g_verr.fail(ORBX_EINVAL, "bad argument");
   if (k < 0 || L < 1 || scoring < 0 || scoring > 5 || weighting < 0 || weighting > 3)
-    return vfail(ORBX_EINVAL, "bad vocabulary header (k %d, L %d, scoring %d, weighting %d)", k, L, scoring,
+    return g_verr.fail(ORBX_EINVAL, "bad vocabulary header (k %d, L %d, scoring %d, weighting %d)", k, L, scoring,
                  weighting);
   // children in file order (loadFromTextFile :1389-1390); node 0 is the root
   std::vector<std::vector<int>> ch(n_nodes);
   for (int i = 1; i < n_nodes; ++i) {
-    if (parent[i] < 0 || parent[i] >= i) return vfail(ORBX_EINVAL, "node %d: parent %d is not an earlier node", i, parent[i]);
+    if (parent[i] < 0 || parent[i] >= i) return g_verr.fail(ORBX_EINVAL, "node %d: parent %d is not an earlier node", i, parent[i]);
     ch[parent[i]].push_back(i);
   }
   // breadth-first renumbering: the children of a node get consecutive ids
@@ -436,8 +410,8 @@ int orbv_create(int k, int L, int scoring, int weighting, int n_nodes, const int
     hword[j] = wid[o];  // Node(): word_id(0) for nodes that are not words
     horig[j] = (uint32_t)o;
   }
-  if (maxc > 65535) return vfail(ORBX_EINVAL, "a node has more than 65535 children");
-  if (hipSetDevice(device) != hipSuccess) return vfail(ORBX_EDEVICE, "no device %d", device);
+  if (maxc > 65535) return g_verr.fail(ORBX_EINVAL, "a node has more than 65535 children");
+  if (hipSetDevice(device) != hipSuccess) return g_verr.fail(ORBX_EDEVICE, "no device %d", device);
   orbv_vocabulary* v = new orbv_vocabulary();
   v->device = device;
   v->k = k;
@@ -452,7 +426,7 @@ int orbv_create(int k, int L, int scoring, int weighting, int n_nodes, const int
       hipMalloc(&v->word, n_nodes * 4) != hipSuccess || hipMalloc(&v->weight, n_nodes * 8) != hipSuccess ||
       hipMalloc(&v->orig, n_nodes * 4) != hipSuccess) {
     orbv_destroy(v);
-    return vfail(ORBX_ENOMEM, "vocabulary allocation failed (%d nodes)", n_nodes);
+    return g_verr.fail(ORBX_ENOMEM, "vocabulary allocation failed (%d nodes)", n_nodes);
   }
   if (hipMemcpy(v->child, hchild.data(), n_nodes * sizeof(int2), hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(v->desc, hdesc.data(), (size_t)n_nodes * 32, hipMemcpyHostToDevice) != hipSuccess ||
@@ -460,7 +434,7 @@ int orbv_create(int k, int L, int scoring, int weighting, int n_nodes, const int
       hipMemcpy(v->weight, hweight.data(), n_nodes * 8, hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(v->orig, horig.data(), n_nodes * 4, hipMemcpyHostToDevice) != hipSuccess) {
     orbv_destroy(v);
-    return vfail(ORBX_EDEVICE, "vocabulary upload failed");
+    return g_verr.fail(ORBX_EDEVICE, "vocabulary upload failed");
   }
   *out = v;
   return ORBX_OK;
@@ -468,9 +442,9 @@ int orbv_create(int k, int L, int scoring, int weighting, int n_nodes, const int
 
 int orbv_load_text(const char* path, int device, orbv_handle* out) {
   // TemplatedVocabulary::loadFromTextFile (TemplatedVocabulary.h:1338-1418)
-  if (!path || !out) return vfail(ORBX_EINVAL, "bad argument");
+  if (!path || !out) return g_verr.fail(ORBX_EINVAL, "bad argument");
   FILE* fp = fopen(path, "rb");
-  if (!fp) return vfail(ORBX_EINVAL, "cannot open %s", path);
+  if (!fp) return g_verr.fail(ORBX_EINVAL, "cannot open %s", path);
   std::vector<char> buf;
   {
     fseek(fp, 0, SEEK_END);
@@ -492,7 +466,7 @@ int orbv_load_text(const char* path, int device, orbv_handle* out) {
   int k = 0, L = 0, n1 = 0, n2 = 0;
   if (sscanf(p, "%d %d %d %d", &k, &L, &n1, &n2) != 4 || k < 0 || k > 20 || L < 1 || L > 10 || n1 < 0 ||
       n1 > 5 || n2 < 0 || n2 > 3)
-    return vfail(ORBX_EINVAL, "%s: not a vocabulary text file (header)", path);
+    return g_verr.fail(ORBX_EINVAL, "%s: not a vocabulary text file (header)", path);
   *e = save;
   p = *e ? e + 1 : e;
   std::vector<int> parent{0};
@@ -511,7 +485,7 @@ int orbv_load_text(const char* path, int device, orbv_handle* out) {
       const long pid = strtol(q, &q, 10);
       const long isl = strtol(q, &q, 10);
       const int nid = (int)parent.size();
-      if (pid < 0 || pid >= nid) return vfail(ORBX_EINVAL, "%s:%d: bad parent %ld", path, lineno, pid);
+      if (pid < 0 || pid >= nid) return g_verr.fail(ORBX_EINVAL, "%s:%d: bad parent %ld", path, lineno, pid);
       parent.push_back((int)pid);
       leaf.push_back(isl > 0);
       for (int i = 0; i < 32; ++i) desc.push_back((uint8_t)strtol(q, &q, 10));  // FORB::fromString
@@ -525,7 +499,7 @@ int orbv_load_text(const char* path, int device, orbv_handle* out) {
 }
 
 int orbv_info(orbv_handle v, int* k, int* L, int* scoring, int* weighting, int* n_nodes, int* n_words) {
-  if (!v) return vfail(ORBX_EINVAL, "null handle");
+  if (!v) return g_verr.fail(ORBX_EINVAL, "null handle");
   if (k) *k = v->k;
   if (L) *L = v->L;
   if (scoring) *scoring = v->scoring;
@@ -541,16 +515,16 @@ int orbv_transform_batch(orbv_handle v, const uint8_t* d_desc, size_t desc_pitch
                          uint32_t* d_node_ids, double* d_weights, void* stream) {
   if (!v || !d_desc || !d_n || frames < 1 || cap < 1 || !d_bow_words || !d_bow_values || !d_bow_n || !d_fv_nodes ||
       !d_fv_off || !d_fv_idx || !d_fv_n)
-    return vfail(ORBX_EINVAL, "bad argument");
-  if (cap > 8192) return vfail(ORBX_ECAPACITY, "cap %d > 8192 features per frame", cap);
-  if (desc_pitch < (size_t)cap * 32 || (desc_pitch & 15)) return vfail(ORBX_EINVAL, "bad descriptor pitch");
-  VHIP(hipSetDevice(v->device));
+    return g_verr.fail(ORBX_EINVAL, "bad argument");
+  if (cap > 8192) return g_verr.fail(ORBX_ECAPACITY, "cap %d > 8192 features per frame", cap);
+  if (desc_pitch < (size_t)cap * 32 || (desc_pitch & 15)) return g_verr.fail(ORBX_EINVAL, "bad descriptor pitch");
+  HIP_OK(g_verr, hipSetDevice(v->device));
   hipStream_t st = (hipStream_t)stream;
   const size_t nf = (size_t)frames * cap;
   if (!d_word_ids || !d_node_ids || !d_weights) {
-    int rc;
-    if ((rc = ws_reserve(v, nf * 16))) return rc;
-    d_weights = (double*)v->ws;
+    if (const hipError_t e = v->ws.reserve(nf * 16))
+      return g_verr.fail(ORBX_EDEVICE, "hipMalloc(&v->ws, bytes): %s", hipGetErrorString(e));
+    d_weights = v->ws.as<double>();
     d_word_ids = (uint32_t*)(d_weights + nf);
     d_node_ids = d_word_ids + nf;
   }
@@ -574,7 +548,7 @@ int orbv_transform_batch(orbv_handle v, const uint8_t* d_desc, size_t desc_pitch
       hipLaunchKernelGGL(voc_descend_kernel<32>, dim3((unsigned)((groups * 32 + 255) / 256)), dim3(256), 0, st, V,
                          d_desc, desc_pitch, d_n, frames, cap, nid_level, d_word_ids, d_node_ids, d_weights);
     }
-    VHIP(hipGetLastError());
+    HIP_OK(g_verr, hipGetLastError());
   }
   int voc_stop = 0;
 #ifdef ORBX_DIAG  // diagnostics builds only: 1 = descend only, 2 = FeatureVector only, 3 = no normalisation
@@ -585,7 +559,7 @@ int orbv_transform_batch(orbv_handle v, const uint8_t* d_desc, size_t desc_pitch
   while (S < cap) S <<= 1;
   const size_t lds = (size_t)S * 12;
   if (raise_lds_limit((const void*)voc_assemble_kernel, lds))
-    return vfail(ORBX_EDEVICE, "hipFuncSetAttribute(voc_assemble_kernel): %s", hipGetErrorString(hipGetLastError()));
+    return g_verr.fail(ORBX_EDEVICE, "hipFuncSetAttribute(voc_assemble_kernel): %s", hipGetErrorString(hipGetLastError()));
   int l1 = v->scoring != 1;
   const int must = v->scoring != 5;
   const int tf = v->weighting == 0 || v->weighting == 1;
@@ -593,7 +567,7 @@ int orbv_transform_batch(orbv_handle v, const uint8_t* d_desc, size_t desc_pitch
                      d_weights, tf, must, !l1, v->n_words, d_bow_words, d_bow_values, d_bow_n, d_fv_nodes, d_fv_off,
                      d_fv_idx, d_fv_n,
                      voc_stop);
-  VHIP(hipGetLastError());
+  HIP_OK(g_verr, hipGetLastError());
   return ORBX_OK;
 }
 
@@ -601,9 +575,9 @@ int orbv_transform(orbv_handle v, const uint8_t* desc, int n, int levelsup, uint
                    int* bow_n, uint32_t* fv_nodes, int* fv_off, int* fv_idx, int* fv_n, uint32_t* word_ids,
                    uint32_t* node_ids, double* weights) {
   if (!v || n < 0 || (n && !desc) || !bow_n || !fv_n || !fv_off || (n && (!bow_words || !bow_values || !fv_nodes || !fv_idx)))
-    return vfail(ORBX_EINVAL, "bad argument");
-  if (n > 8192) return vfail(ORBX_ECAPACITY, "more than 8192 features");
-  VHIP(hipSetDevice(v->device));
+    return g_verr.fail(ORBX_EINVAL, "bad argument");
+  if (n > 8192) return g_verr.fail(ORBX_ECAPACITY, "more than 8192 features");
+  HIP_OK(g_verr, hipSetDevice(v->device));
   const int cap = std::max(n, 1);
   // staging: desc | n | bow words | bow values | fv nodes | fv off | fv idx | counts | per-feature
   const size_t dpitch = ((size_t)cap * 32 + 15) & ~(size_t)15;
@@ -616,15 +590,15 @@ int orbv_transform(orbv_handle v, const uint8_t* desc, int n, int levelsup, uint
     tot += (s + 255) & ~(size_t)255;
   }
   void* stage = nullptr;
-  VHIP(hipMalloc(&stage, tot));
+  HIP_OK(g_verr, hipMalloc(&stage, tot));
   uint8_t* b = (uint8_t*)stage;
   auto at = [&](int i) { return (void*)(b + off[i]); };
-  if (!v->stream) VHIP(hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking));
+  if (!v->stream) HIP_OK(g_verr, hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking));
   hipStream_t st = v->stream;
   int rc = ORBX_OK;
   do {
-    if (n && hipMemcpyAsync(at(0), desc, (size_t)n * 32, hipMemcpyHostToDevice, st) != hipSuccess) { rc = vfail(ORBX_EDEVICE, "upload"); break; }
-    if (hipMemcpyAsync(at(1), &n, 4, hipMemcpyHostToDevice, st) != hipSuccess) { rc = vfail(ORBX_EDEVICE, "upload"); break; }
+    if (n && hipMemcpyAsync(at(0), desc, (size_t)n * 32, hipMemcpyHostToDevice, st) != hipSuccess) { rc = g_verr.fail(ORBX_EDEVICE, "upload"); break; }
+    if (hipMemcpyAsync(at(1), &n, 4, hipMemcpyHostToDevice, st) != hipSuccess) { rc = g_verr.fail(ORBX_EDEVICE, "upload"); break; }
     int* cnt = (int*)at(7);
     rc = orbv_transform_batch(v, (const uint8_t*)at(0), dpitch, (const int*)at(1), 1, cap, levelsup, (uint32_t*)at(2),
                               (double*)at(3), cnt, (uint32_t*)at(4), (int*)at(5), (int*)at(6), cnt + 1,
@@ -632,12 +606,12 @@ int orbv_transform(orbv_handle v, const uint8_t* desc, int n, int levelsup, uint
     if (rc) break;
     int hc[2] = {0, 0};
     if (hipMemcpyAsync(hc, cnt, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess) { rc = vfail(ORBX_EDEVICE, "transform failed"); break; }
+        hipStreamSynchronize(st) != hipSuccess) { rc = g_verr.fail(ORBX_EDEVICE, "transform failed"); break; }
     *bow_n = hc[0];
     *fv_n = hc[1];
     int nfeat = 0;
     if (hipMemcpyAsync(fv_off, at(5), (size_t)(hc[1] + 1) * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess) { rc = vfail(ORBX_EDEVICE, "download"); break; }
+        hipStreamSynchronize(st) != hipSuccess) { rc = g_verr.fail(ORBX_EDEVICE, "download"); break; }
     nfeat = fv_off[hc[1]];
     if ((hc[0] && (hipMemcpyAsync(bow_words, at(2), (size_t)hc[0] * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
                    hipMemcpyAsync(bow_values, at(3), (size_t)hc[0] * 8, hipMemcpyDeviceToHost, st) != hipSuccess)) ||
@@ -646,7 +620,7 @@ int orbv_transform(orbv_handle v, const uint8_t* desc, int n, int levelsup, uint
         (n && word_ids && hipMemcpyAsync(word_ids, at(8), (size_t)n * 4, hipMemcpyDeviceToHost, st) != hipSuccess) ||
         (n && node_ids && hipMemcpyAsync(node_ids, at(9), (size_t)n * 4, hipMemcpyDeviceToHost, st) != hipSuccess) ||
         (n && weights && hipMemcpyAsync(weights, at(10), (size_t)n * 8, hipMemcpyDeviceToHost, st) != hipSuccess) ||
-        hipStreamSynchronize(st) != hipSuccess) { rc = vfail(ORBX_EDEVICE, "download"); break; }
+        hipStreamSynchronize(st) != hipSuccess) { rc = g_verr.fail(ORBX_EDEVICE, "download"); break; }
   } while (0);
   (void)hipFree(stage);
   return rc;

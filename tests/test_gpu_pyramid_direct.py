@@ -3,7 +3,7 @@
 The kernel takes a thread's column set-up per level (the dword-pair offsets of
 its 4 runs in the source level's LDS rows, 8 byte selectors, 8 coefficient
 pairs and its store flags) from records the host makes at plan time
-(orbx_host.hip plan_band_pyramid). This file was written for a first design,
+(orbx_plan.hip plan_band_pyramid). This file was written for a first design,
 level 1 loaded straight from the frame with no level-0 tile in LDS, which its
 own bound measurement ruled out; its cases (widths around
 the 16-byte chunks of level 0's staging, 4-byte and odd bases and row strides,
@@ -176,7 +176,7 @@ def test_same_launch_twice(pkg, O, monkeypatch):
 
 # ---------------------------------------------------------------- without a GPU
 def _plan_check(W, H, nl, sf, B):
-    """[records checked of kept plan i, -1 where a bound fails] (orbx_host.hip pyr_records_ok)."""
+    """[records checked of kept plan i, -1 where a bound fails] (orbx_plan.hip pyr_records_ok)."""
     import orb_slam_cuda_amd as pkg
     from orb_slam_cuda_amd._lib import OrbxConfig
     f = pkg.lib().orbx_pyr_plan_check

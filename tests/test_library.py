@@ -141,27 +141,6 @@ def test_prepare_pose_level_mode():
     assert np.allclose(np.array(p.Rt).reshape(3, 4), T)
 
 
-def test_fast_frame_index_magic_is_exact():
-    """FAST's frame index (orbx_fast.hip) is mulhi(id, m) with m = ceil(2^32 / d),
-    d = cells per frame, which orbx_host.hip enables only while
-    d * B * (m * d - 2^32) < 2^32. Checked here at the worst ids (the last
-    id of each frame, where the remainder is d - 1) for every d the planner can
-    produce and the largest B that passes the check, plus a random sample."""
-    import numpy as np
-    rng = np.random.default_rng(7)
-    for d in list(range(2, 5001)) + [8191, 12000, 40000]:
-        m = ((1 << 32) + d - 1) // d
-        e = m * d - (1 << 32)
-        bmax = ((1 << 32) - 1) // (d * e) if e else 1 << 20
-        bmax = min(bmax, 1 << 14)
-        if bmax < 1:
-            continue
-        ids = [(q + 1) * d - 1 for q in range(0, bmax, max(1, bmax // 64))] + [d * bmax - 1]
-        ids += [int(x) for x in rng.integers(0, d * bmax, 16)]
-        for i in ids:
-            assert (i * m) >> 32 == i // d, (d, bmax, i)
-
-
 def test_brief_cvround_by_magic_add():
     """orient_brief_kernel rounds a test coordinate with fl(v + 1.5 * 2^23) and
     reads the integer from the sum's bit pattern; the reference's cvRound is

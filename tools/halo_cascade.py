@@ -4,7 +4,7 @@ rows of every level a band must compute when it only feeds the next level
 (halo 0, the shipped plan) and when it must also blur its own rows in LDS
 (halo 3 at every level, which cascades: each halo row of level l+1 needs its
 INTER_LINEAR source rows of level l). Same row tables as plan_band_pyramid
-(orbx_host.hip): OpenCV 3.x INTER_LINEAR source rows per output row.
+(orbx_plan.hip): OpenCV 3.x INTER_LINEAR source rows per output row.
 Usage: python tools/halo_cascade.py [R]"""
 import math
 import sys

@@ -1,4 +1,4 @@
-"""Host-side model of the band pyramid's tilings (orbx_host.hip
+"""Host-side model of the band pyramid's tilings (orbx_plan.hip
 plan_band_pyramid / plan_pyr_cols restated): per (bands, column tiles) the
 worst tile's pixel count and row-loop iterations, for fitting the plan
 picker's cost rule against tools/pyr_plans.py timings.
