@@ -83,6 +83,8 @@
  *                          include/ORBmatcher.h:72, src/ORBmatcher.cc:657-823
  *   orbm_pose_optimization / _batch / _host  Optimizer::PoseOptimization(Frame*)
  *                          include/Optimizer.h:53, src/Optimizer.cc:334-543
+ *   orbm_sim3_ransac / _batch / _host  Sim3Solver (ctor, SetRansacParameters,
+ *                          iterate / find)  include/Sim3Solver.h, src/Sim3Solver.cc:37-423
  *   orbv_load_text / orbv_create  ORBVocabulary::loadFromTextFile
  *                          (DBoW2 TemplatedVocabulary, include/ORBVocabulary.h:30,
  *                          Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1338-1418)
@@ -307,7 +309,11 @@ int orbm_destroy(orbm_handle m);
  * 128: orbm_refresh_map_points_batch / orbm_refresh_map_points skipped a
  * point whose list names a keyframe, descriptor row or octave out of range;
  * bit 256: orbm_pose_optimization_batch / orbm_pose_optimization left out a
- * keypoint whose octave or map point row is out of range).
+ * keypoint whose octave or map point row is out of range; bit 512:
+ * orbm_sim3_ransac_batch / orbm_sim3_ransac treated an entry as unmatched
+ * because its match12 or kp_index1 value is at or above the keyframe's
+ * count, its keypoint's octave is outside [0, nlevels), or the gathered
+ * list would not fit the pitch).
  * SearchForInitialization keeps no
  * candidate lists (8 smallest keys per query) and never sets it. Waits for
  * the matcher's own launches that may set it (on whatever streams they ran),
@@ -812,6 +818,125 @@ int orbm_pose_optimization_batch(orbm_handle m, const orbx_kp* d_kps, const int*
                                  const float* inv_sigma2, int nlevels, const orbm_camera* d_cams,
                                  int frames, int flags, float* d_Tcw, orbm_pose* d_pose,
                                  uint8_t* d_outlier, orbm_poseopt_result* d_result, void* stream);
+
+/* ------------------------------------------------------------ Sim3Solver
+ * Loop closing's RANSAC between SearchByBoW and SearchBySim3
+ * (src/LoopClosing.cc:313-340): the constructor's gather (src/Sim3Solver.cc:
+ * 37-112), SetRansacParameters (:114-138), iterate / find (:140-213),
+ * ComputeSim3 (:226-337) and CheckInliers (:340-423) as one call. All
+ * hypotheses are computed; the reference's early exit is the first iteration
+ * whose inlier count is > min_inliers and >= the best so far.
+ *
+ * Inputs per keyframe pair: kps1 / kps2 = mvKeysUn (only octave is read), n1 /
+ * n2 their counts; mps1 / mps2 = one orbm_map_point_world per keypoint
+ * (GetMapPointMatches(): pos is read, valid = pMP && !isBad()); cam1 / cam2 =
+ * fx, fy, cx, cy, mbf of each keyframe with Tcw = rows 0..2 of its pose (T1w,
+ * T2w); match12[i1] = the keypoint index in KF2 matched to keypoint i1 of KF1,
+ * or < 0 (the d_out of orbm_search_by_bow_batch with kf_vs_kf = 1, the match12
+ * of orbm_search_by_sim3); kp_index1 (may be NULL = identity) =
+ * pMP1->GetIndexInKeyFrame(pKF1) of the point at i1, the keypoint whose octave
+ * is read (a negative value leaves i1 out, as the reference's `continue`);
+ * level_sigma2 = mvLevelSigma2 (nlevels <= 16 floats, host).
+ * Entry i1 is a correspondence when match12[i1] >= 0, mps1[i1].valid and
+ * mps2[match12[i1]].valid; the correspondences keep the order of i1.
+ * rand3[max_iterations][3]: the raw rand() values of the three draws of each
+ * iteration (orbm_sim3_rand_fill), not indices: the call applies
+ * DUtils::Random::RandomInt and the draw without replacement itself, on the
+ * count of correspondences it finds.
+ * A match12 value >= n2, a kp_index1 value >= n1 or an octave outside
+ * [0, nlevels) makes the entry unmatched and sets status bit 512.
+ *
+ * Outputs (each may be NULL): *result below; s12, R12[9] (row-major), t12[3] of
+ * the accepted hypothesis, or of the running best when none is accepted, left
+ * untouched when result.best_iteration < 0; pose[2] = orbm_prepare_sim3_match(
+ * cam1, T1w, T2w, s12, R12, t12), byte for byte, written when s12 is;
+ * inlier[i1] for every i1 < n1: 1 where vbInliers of the accepted hypothesis
+ * is set, all 0 when none is accepted; hyp[h] for every hypothesis h that ran
+ * (first_iteration <= h < result.max_its). Fewer than 3 correspondences are
+ * treated as fewer than min_inliers. */
+typedef struct orbm_sim3_params {
+  double probability;      /* SetRansacParameters(probability, minInliers, maxIterations) */
+  int32_t min_inliers;
+  int32_t max_iterations;  /* 1 .. 1024 (orbm_sim3_limits) */
+  int32_t fix_scale;       /* mbFixScale */
+  int32_t first_iteration; /* 0-based; 0 on a fresh solver, result.iterations to resume */
+  int32_t best_inliers;    /* mnBestInliers on entry: 0 on a fresh solver */
+  int32_t reserved;
+} orbm_sim3_params; /* 32 B */
+
+typedef struct orbm_sim3_result {
+  int32_t ret;            /* nInliers of the accepted hypothesis, else 0 */
+  int32_t iterations;     /* mnIterations on return: accepted index + 1, or mRansacMaxIts */
+  int32_t no_more;        /* bNoMore: nothing was accepted and no iteration is left */
+  int32_t n_corr;         /* N */
+  int32_t max_its;        /* mRansacMaxIts; 0 when N < min_inliers */
+  int32_t best_inliers;   /* mnBestInliers on return */
+  int32_t best_iteration; /* the iteration (0-based) that set it, ties to the later one; -1: none in this call */
+  int32_t reserved;
+} orbm_sim3_result; /* 32 B */
+
+typedef struct orbm_sim3_hyp {
+  int32_t idx[3]; /* the three draws, positions in the gathered list */
+  int32_t count;  /* mnInliersi */
+  float s, R[9], t[3];
+} orbm_sim3_hyp; /* 68 B */
+
+/* 3 x rand() per iteration, in order: the reference's stream. Host only. */
+int orbm_sim3_rand_fill(uint32_t* out, int iterations);
+/* The cap of max_iterations, the hypotheses per workgroup and the largest
+ * pitch whose gathered list stays in LDS (each may be NULL). Host only. */
+int orbm_sim3_limits(int* max_iterations, int* chunk, int* lds_pitch);
+/* out[N] = mRansacMaxIts for N = 0 .. n_max correspondences (0 where N <
+ * max(min_inliers, 3)): ceil(log(1 - p) / log(1 - pow((float)min_inliers / N,
+ * 3))) with the host's libm, 1 when N == min_inliers, limited to [1,
+ * max_iterations]. The device calls look their count up in this table.
+ * Host only. */
+int orbm_sim3_iteration_table(double probability, int min_inliers, int max_iterations, int n_max,
+                              int* out);
+
+/* Host only: runs without a device, n1 / n2 not bounded by a handle. *status
+ * (may be NULL) gets 0 or bit 512. With hyp == NULL it stops at the first
+ * accepted hypothesis, as the reference does; the outputs are the same. */
+int orbm_sim3_ransac_host(const orbx_kp* kps1, int n1, const orbx_kp* kps2, int n2,
+                          const orbm_map_point_world* mps1, const orbm_map_point_world* mps2,
+                          const orbm_camera* cam1, const orbm_camera* cam2, const int* match12,
+                          const int* kp_index1, const float* level_sigma2, int nlevels,
+                          const orbm_sim3_params* params, const uint32_t* rand3,
+                          orbm_sim3_result* result, float* s12, float* R12, float* t12,
+                          orbm_pose* pose, uint8_t* inlier, orbm_sim3_hyp* hyp, int* status);
+
+/* The same on the device from host arrays, synchronous, one round trip.
+ * n1, n2 <= max_kps. Counts, flags and everything after a hypothesis's
+ * (s, R, t) are those of the same arithmetic; (s, R, t) may differ from the
+ * host form's where the device's atan2 / sin / cos round differently. Status
+ * bit 512 is left for orbm_get_status. */
+int orbm_sim3_ransac(orbm_handle m, const orbx_kp* kps1, int n1, const orbx_kp* kps2, int n2,
+                     const orbm_map_point_world* mps1, const orbm_map_point_world* mps2,
+                     const orbm_camera* cam1, const orbm_camera* cam2, const int* match12,
+                     const int* kp_index1, const float* level_sigma2, int nlevels,
+                     const orbm_sim3_params* params, const uint32_t* rand3,
+                     orbm_sim3_result* result, float* s12, float* R12, float* t12, orbm_pose* pose,
+                     uint8_t* inlier, orbm_sim3_hyp* hyp);
+
+/* Device-resident and asynchronous on `stream`. Pair p's keypoints, match12,
+ * kp_index1 and inlier at p*kp_pitch (d_n1[p] / d_n2[p] of them), its map
+ * points at p*mp_pitch (one row per keypoint, mp_pitch >= kp_pitch), its
+ * cameras d_cam1[p] / d_cam2[p], its draws at d_rand3 + p*3*max_iterations,
+ * its diagnostics at d_hyp + p*max_iterations; d_result[p], d_s12[p], d_R12 +
+ * 9*p, d_t12 + 3*p, d_pose + 2*p. params holds for every pair. inlier slots
+ * from d_n1[p] on are not touched; empty pairs are valid anywhere in the
+ * batch. kp_pitch <= max_kps; the gathered list stays in LDS up to a pitch of
+ * 1024, above that in the handle's workspace. The output bits of a pair do
+ * not depend on the batch size, its slot, the run or the pitch. */
+int orbm_sim3_ransac_batch(orbm_handle m, const orbx_kp* d_kps1, const int* d_n1,
+                           const orbx_kp* d_kps2, const int* d_n2, int kp_pitch,
+                           const orbm_map_point_world* d_mps1, const orbm_map_point_world* d_mps2,
+                           int mp_pitch, const orbm_camera* d_cam1, const orbm_camera* d_cam2,
+                           const int* d_match12, const int* d_kp_index1, const float* level_sigma2,
+                           int nlevels, const orbm_sim3_params* params, const uint32_t* d_rand3,
+                           int pairs, orbm_sim3_result* d_result, float* d_s12, float* d_R12,
+                           float* d_t12, orbm_pose* d_pose, uint8_t* d_inlier, orbm_sim3_hyp* d_hyp,
+                           void* stream);
 
 /* DBoW2::FeatureVector as CSR: nodes[k] ascending NodeIds; the feature
  * indices of node k are idx[off[k] .. off[k+1]). Each feature index appears

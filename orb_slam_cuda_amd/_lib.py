@@ -244,6 +244,17 @@ def lib() -> C.CDLL:
         L.orbm_pose_optimization_batch.argtypes = (
             [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                                                 C.c_int] + [C.c_void_p] * 5)
+        # kps1, n1, kps2, n2, mps1, mps2, cam1, cam2, match12, kp_index1, level_sigma2, nlevels, params, rand3,
+        # result, s12, R12, t12, pose, inlier, hyp
+        S3 = ([C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 7 + [C.c_int] + [C.c_void_p] * 9)
+        L.orbm_sim3_ransac_host.argtypes = S3 + [C.POINTER(C.c_int)]
+        L.orbm_sim3_ransac.argtypes = [C.c_void_p] + S3
+        L.orbm_sim3_ransac_batch.argtypes = ([C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 2 + [C.c_int] +
+                                             [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 2 + [C.c_int] +
+                                             [C.c_void_p] * 8)
+        L.orbm_sim3_rand_fill.argtypes = [C.c_void_p, C.c_int]
+        L.orbm_sim3_limits.argtypes = [C.POINTER(C.c_int)] * 3
+        L.orbm_sim3_iteration_table.argtypes = [C.c_double, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.orbm_prepare_sim3_match.argtypes = [C.POINTER(OrbmCamera), C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
                                               C.c_void_p, C.POINTER(OrbmPose)]
         L.orbm_fuse.argtypes = (PS + [C.c_void_p, GridBounds, C.c_void_p, C.c_void_p, C.c_int, C.c_float,
@@ -352,6 +363,53 @@ POSEOPT_RESULT_DTYPE = np.dtype([("ret", "<i4"), ("n_initial", "<i4"), ("n_bad",
                                  ("rejected", "<i4"), ("reserved", "<i4")])
 assert POSEOPT_RESULT_DTYPE.itemsize == 32
 POSEOPT_DISCARD_OUTLIERS = 1
+# orbm_sim3_params, orbm_sim3_result, orbm_sim3_hyp (include/orbx_c.h): 32, 32 and 68 bytes
+SIM3_PARAMS_DTYPE = np.dtype([("probability", "<f8"), ("min_inliers", "<i4"), ("max_iterations", "<i4"),
+                              ("fix_scale", "<i4"), ("first_iteration", "<i4"), ("best_inliers", "<i4"),
+                              ("reserved", "<i4")])
+SIM3_RESULT_DTYPE = np.dtype([("ret", "<i4"), ("iterations", "<i4"), ("no_more", "<i4"), ("n_corr", "<i4"),
+                              ("max_its", "<i4"), ("best_inliers", "<i4"), ("best_iteration", "<i4"),
+                              ("reserved", "<i4")])
+SIM3_HYP_DTYPE = np.dtype([("idx", "<i4", (3,)), ("count", "<i4"), ("s", "<f4"), ("R", "<f4", (9,)),
+                           ("t", "<f4", (3,))])
+assert SIM3_PARAMS_DTYPE.itemsize == 32 and SIM3_RESULT_DTYPE.itemsize == 32 and SIM3_HYP_DTYPE.itemsize == 68
+CAMERA_DTYPE = np.dtype([("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"), ("mb", "<f4"), ("mbf", "<f4"),
+                         ("Tcw", "<f4", (12,))])  # orbm_camera as an array element (the batch calls)
+POSE_DTYPE = np.dtype([("Rt", "<f4", (12,)), ("Ow", "<f4", (3,)), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"),
+                       ("cy", "<f4"), ("mbf", "<f4"), ("level_mode", "<i4"), ("Rt2", "<f4", (12,))])  # orbm_pose
+assert CAMERA_DTYPE.itemsize == 72 and POSE_DTYPE.itemsize == 132
+STATUS_SIM3_SKIPPED = 512
+
+
+def sim3_params(probability=0.99, min_inliers=20, max_iterations=300, fix_scale=False, first_iteration=0,
+                best_inliers=0) -> np.ndarray:
+    """One orbm_sim3_params record (SetRansacParameters' three, mbFixScale and the resume state)."""
+    p = np.zeros(1, SIM3_PARAMS_DTYPE)
+    p[0] = (probability, min_inliers, max_iterations, int(bool(fix_scale)), first_iteration, best_inliers, 0)
+    return p
+
+
+def sim3_rand_fill(iterations: int) -> np.ndarray:
+    """(iterations, 3) uint32: 3 x rand() per iteration from the C library's stream (orbm_sim3_rand_fill)."""
+    out = np.zeros((max(iterations, 0), 3), np.uint32)
+    check(lib().orbm_sim3_rand_fill(ptr(out), iterations), matcher=True)
+    return out
+
+
+def sim3_limits() -> tuple[int, int, int]:
+    """(cap of max_iterations, hypotheses per workgroup, largest pitch whose gathered list stays in LDS)."""
+    a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
+    check(lib().orbm_sim3_limits(C.byref(a), C.byref(b), C.byref(c)), matcher=True)
+    return a.value, b.value, c.value
+
+
+def sim3_iteration_table(probability, min_inliers, max_iterations, n_max) -> np.ndarray:
+    """mRansacMaxIts for 0..n_max correspondences (orbm_sim3_iteration_table)."""
+    out = np.zeros(n_max + 1, np.int32)
+    check(lib().orbm_sim3_iteration_table(probability, min_inliers, max_iterations, n_max, ptr(out)), matcher=True)
+    return out
+
+
 OBSERVATION_DTYPE = np.dtype([("kf", "<u4"), ("desc_row", "<u4")])
 KEYFRAME_REF_DTYPE = np.dtype([("Ow", "<f4", (3,)), ("bad", "<u4")])
 POINT_REFKF_DTYPE = np.dtype([("kf", "<u4"), ("octave", "<i4")])

@@ -396,6 +396,38 @@ struct PoseOptArgs {
 };
 size_t poseopt_spill_bytes(int kp_pitch, int frames);  // workspace of a launch (0 up to kPoLdsEdges)
 int launch_pose_optimization(const PoseOptArgs& P, void* spill, void* stream);
+// orbx_sim3.hip — Sim3Solver: the RANSAC of one keyframe pair per grid row (the
+// arithmetic, the limits and status bit 512 are in orbx_sim3.cuh)
+struct Sim3LaunchArgs {
+  const orbx_kp *kps1, *kps2;
+  const int *n1, *n2;
+  int kp_pitch, mp_pitch;
+  const orbm_map_point_world *mps1, *mps2;
+  const orbm_camera *cam1, *cam2;
+  const int* match12;
+  const int* kp_index1;       // or null
+  const float* level_sigma2;  // host, nlevels
+  int nlevels;
+  orbm_sim3_params params;
+  const int* its_tab;  // device: mRansacMaxIts per count 0..kp_pitch (sim3_iterations)
+  const uint32_t* rand3;
+  int pairs;
+  orbm_sim3_result* result;  // every output or null
+  float *s12, *R12, *t12;
+  orbm_pose* pose;
+  uint8_t* inlier;
+  orbm_sim3_hyp* hyp;
+  int* err;  // the handle's status word
+};
+// workspace of a launch: the hypotheses' records, then the gathered lists of pitches above kSim3LdsCorr (else 0)
+void sim3_ws_bytes(int kp_pitch, int pairs, int max_iterations, size_t* hyp_bytes, size_t* rec_bytes);
+int launch_sim3_ransac(const Sim3LaunchArgs& P, void* ws, void* stream);
+int sim3_iterations(double probability, int min_inliers, int max_iterations, int N);
+int sim3_ransac_host(const orbx_kp* kps1, int n1, const orbx_kp* kps2, int n2, const orbm_map_point_world* mps1,
+                     const orbm_map_point_world* mps2, const orbm_camera* cam1, const orbm_camera* cam2,
+                     const int* match12, const int* kp_index1, const float* level_sigma2, int nlevels,
+                     const orbm_sim3_params* params, const uint32_t* rand3, orbm_sim3_result* result, float* s12,
+                     float* R12, float* t12, orbm_pose* pose, uint8_t* inlier, orbm_sim3_hyp* hyp, int* status);
 // orbx_triangulate.hip — SearchForTriangulation, one keyframe pair per workgroup
 struct TriSide {  // one side of the pairs; pitches of 0 share one keyframe across pairs
   const orbx_kp* kps;

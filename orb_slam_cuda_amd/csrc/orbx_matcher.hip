@@ -3,7 +3,7 @@
 // host-array entry points staged through the handle's arena. The kernels are in
 // orbx_top2.hip, orbx_bow.hip, orbx_init.hip, orbx_stereo.hip,
 // orbx_project.hip, orbx_project_pose.hip, orbx_frustum.hip,
-// orbx_triangulate.hip, orbx_mappoint.hip and orbx_poseopt.hip.
+// orbx_triangulate.hip, orbx_mappoint.hip, orbx_poseopt.hip and orbx_sim3.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -21,6 +21,7 @@
 #include "orbx_mappoint.cuh"
 #include "orbx_posemath.cuh"
 #include "orbx_poseopt.cuh"
+#include "orbx_sim3.cuh"
 
 using namespace orbx;
 
@@ -46,9 +47,14 @@ struct orbx_matcher {
   DeviceBuf view_ws;     // SearchLocalPoints: isInFrustum records, then the points in view compacted
   DeviceBuf refresh_ws;  // RefreshMapPoints: class counters and work lists
   DeviceBuf po_ws;       // PoseOptimization: edge records of frame pitches above kPoLdsEdges
+  DeviceBuf sim3_ws;     // Sim3Solver: the hypotheses' records, gathered lists of pitches above kSim3LdsCorr
+  DeviceBuf sim3_tab;    // Sim3Solver: mRansacMaxIts per count, of the parameters below
+  std::vector<int> sim3_tab_host;  // its source (the upload reads it)
+  double sim3_prob = 0;
+  int sim3_min_inliers = -1, sim3_max_iterations = -1;
   hipStream_t stream = nullptr;
-  WsOrder ws;  // stream order of cand / stereo_sad / pose_picks / view_ws / refresh_ws / po_ws / bow_* across caller streams
-  // streams of the launches that may set `err` (top-2, SearchByBoW, SearchLocalPoints, RefreshMapPoints, PoseOptimization)
+  WsOrder ws;  // stream order of cand / stereo_sad / pose_picks / view_ws / refresh_ws / po_ws / sim3_* / bow_* across caller streams
+  // streams of the launches that may set `err` (top-2, SearchByBoW, SearchLocalPoints, RefreshMapPoints, PoseOptimization, Sim3Solver)
   StreamMarks errm;
   // staging for the synchronous entry points
   DeviceBuf stage;
@@ -208,7 +214,7 @@ int orbm_destroy(orbm_handle m) {
   m->errm.release();
   // the buffers go before the stream, not with the handle after it
   for (DeviceBuf* b : {&m->init_ws, &m->host_init_ws, &m->err, &m->stereo_sad, &m->bow_hist, &m->bow_rec, &m->pose_picks,
-                       &m->view_ws, &m->refresh_ws, &m->po_ws, &m->stage})
+                       &m->view_ws, &m->refresh_ws, &m->po_ws, &m->sim3_ws, &m->sim3_tab, &m->stage})
     b->release();
   m->h_stage.release();
   if (m->stream) (void)hipStreamDestroy(m->stream);
@@ -1269,6 +1275,161 @@ int orbm_pose_optimization(orbm_handle m, const orbx_kp* kps, int n, const float
   return ORBX_OK;
 }
 
+// ---------------------------------------------------------------- Sim3Solver
+namespace {
+int sim3_check(const orbx_kp* kps1, int n1, const orbx_kp* kps2, int n2, const orbm_map_point_world* mps1,
+               const orbm_map_point_world* mps2, const orbm_camera* cam1, const orbm_camera* cam2, const int* match12,
+               const float* level_sigma2, int nlevels, const orbm_sim3_params* P, const uint32_t* rand3) {
+  if (n1 < 0 || n2 < 0 || !cam1 || !cam2 || !level_sigma2 || nlevels < 1 || nlevels > kMaxLevels || !P || !rand3 ||
+      (n1 && (!kps1 || !mps1 || !match12)) || (n2 && (!kps2 || !mps2)) || P->first_iteration < 0 || P->min_inliers < 0)
+    return g_merr.fail(ORBX_EINVAL, "bad argument");
+  if (P->max_iterations < 1 || P->max_iterations > kSim3MaxIts)
+    return g_merr.fail(ORBX_ECAPACITY, "max_iterations %d outside 1..%d", P->max_iterations, kSim3MaxIts);
+  return ORBX_OK;
+}
+}  // namespace
+
+int orbm_sim3_ransac_host(const orbx_kp* kps1, int n1, const orbx_kp* kps2, int n2, const orbm_map_point_world* mps1,
+                          const orbm_map_point_world* mps2, const orbm_camera* cam1, const orbm_camera* cam2,
+                          const int* match12, const int* kp_index1, const float* level_sigma2, int nlevels,
+                          const orbm_sim3_params* params, const uint32_t* rand3, orbm_sim3_result* result, float* s12,
+                          float* R12, float* t12, orbm_pose* pose, uint8_t* inlier, orbm_sim3_hyp* hyp, int* status) {
+  int rc;
+  if ((rc = sim3_check(kps1, n1, kps2, n2, mps1, mps2, cam1, cam2, match12, level_sigma2, nlevels, params, rand3)))
+    return rc;
+  return sim3_ransac_host(kps1, n1, kps2, n2, mps1, mps2, cam1, cam2, match12, kp_index1, level_sigma2, nlevels, params,
+                          rand3, result, s12, R12, t12, pose, inlier, hyp, status);
+}
+
+int orbm_sim3_ransac_batch(orbm_handle m, const orbx_kp* d_kps1, const int* d_n1, const orbx_kp* d_kps2,
+                           const int* d_n2, int kp_pitch, const orbm_map_point_world* d_mps1,
+                           const orbm_map_point_world* d_mps2, int mp_pitch, const orbm_camera* d_cam1,
+                           const orbm_camera* d_cam2, const int* d_match12, const int* d_kp_index1,
+                           const float* level_sigma2, int nlevels, const orbm_sim3_params* params,
+                           const uint32_t* d_rand3, int pairs, orbm_sim3_result* d_result, float* d_s12, float* d_R12,
+                           float* d_t12, orbm_pose* d_pose, uint8_t* d_inlier, orbm_sim3_hyp* d_hyp, void* stream) {
+  if (!m || !d_kps1 || !d_n1 || !d_kps2 || !d_n2 || !d_mps1 || !d_mps2 || !d_cam1 || !d_cam2 || !d_match12 ||
+      !level_sigma2 || !params || !d_rand3 || pairs < 1 || kp_pitch < 1 || mp_pitch < kp_pitch || nlevels < 1 ||
+      nlevels > kMaxLevels || params->first_iteration < 0 || params->min_inliers < 0)
+    return g_merr.fail(ORBX_EINVAL, "bad argument");
+  if (params->max_iterations < 1 || params->max_iterations > kSim3MaxIts)
+    return g_merr.fail(ORBX_ECAPACITY, "max_iterations %d outside 1..%d", params->max_iterations, kSim3MaxIts);
+  if (kp_pitch > m->max_kps)
+    return g_merr.fail(ORBX_ECAPACITY, "kp_pitch %d above the handle's max_kps %d", kp_pitch, m->max_kps);
+  HIP_OK(g_merr, hipSetDevice(m->device));
+  hipStream_t s = (hipStream_t)stream;
+  size_t hyp_bytes, rec_bytes;
+  sim3_ws_bytes(kp_pitch, pairs, params->max_iterations, &hyp_bytes, &rec_bytes);
+  const size_t need = hyp_bytes + rec_bytes, tab_n = (size_t)kp_pitch + 1;
+  // the workspace and the iteration table are the handle's: after their last user, whatever its stream
+  if (m->ws.before(s)) return g_merr.fail(ORBX_EDEVICE, "stream wait on the workspace failed");
+  const bool new_tab = m->sim3_tab_host.size() < tab_n || m->sim3_prob != params->probability ||
+                       m->sim3_min_inliers != params->min_inliers || m->sim3_max_iterations != params->max_iterations;
+  if (m->sim3_ws.n < need || new_tab) {
+    // replaced memory and a rewritten host table must not be in use: wait for the last user
+    if (m->ws.ev) HIP_OK(g_merr, hipEventSynchronize(m->ws.ev));
+    if (m->sim3_ws.reserve(need) != hipSuccess) return g_merr.fail(ORBX_ENOMEM, "Sim3 workspace");
+  }
+  if (new_tab) {
+    // SetRansacParameters with the host's libm, one entry per count the pitch allows
+    const size_t n = std::max(tab_n, m->sim3_tab_host.size());
+    m->sim3_tab_host.resize(n);
+    for (size_t N = 0; N < n; ++N)
+      m->sim3_tab_host[N] = sim3_iterations(params->probability, params->min_inliers, params->max_iterations, (int)N);
+    m->sim3_prob = params->probability;
+    m->sim3_min_inliers = params->min_inliers;
+    m->sim3_max_iterations = params->max_iterations;
+    if (m->sim3_tab.reserve(n * sizeof(int)) != hipSuccess) return g_merr.fail(ORBX_ENOMEM, "Sim3 iteration table");
+    HIP_OK(g_merr, hipMemcpyAsync(m->sim3_tab.p, m->sim3_tab_host.data(), n * sizeof(int), hipMemcpyHostToDevice, s));
+  }
+  Sim3LaunchArgs A{};
+  A.kps1 = d_kps1;
+  A.kps2 = d_kps2;
+  A.n1 = d_n1;
+  A.n2 = d_n2;
+  A.kp_pitch = kp_pitch;
+  A.mp_pitch = mp_pitch;
+  A.mps1 = d_mps1;
+  A.mps2 = d_mps2;
+  A.cam1 = d_cam1;
+  A.cam2 = d_cam2;
+  A.match12 = d_match12;
+  A.kp_index1 = d_kp_index1;
+  A.level_sigma2 = level_sigma2;
+  A.nlevels = nlevels;
+  A.params = *params;
+  A.its_tab = m->sim3_tab.as<int>();
+  A.rand3 = d_rand3;
+  A.pairs = pairs;
+  A.result = d_result;
+  A.s12 = d_s12;
+  A.R12 = d_R12;
+  A.t12 = d_t12;
+  A.pose = d_pose;
+  A.inlier = d_inlier;
+  A.hyp = d_hyp;
+  A.err = m->err.as<int>();
+  if (launch_sim3_ransac(A, m->sim3_ws.p, stream))
+    return g_merr.fail(ORBX_EDEVICE, "Sim3 launch: %s", hipGetErrorString(hipGetLastError()));
+  if (m->ws.after(s) || m->errm.mark(s)) return g_merr.fail(ORBX_EDEVICE, "event record failed");
+  return ORBX_OK;
+}
+
+int orbm_sim3_ransac(orbm_handle m, const orbx_kp* kps1, int n1, const orbx_kp* kps2, int n2,
+                     const orbm_map_point_world* mps1, const orbm_map_point_world* mps2, const orbm_camera* cam1,
+                     const orbm_camera* cam2, const int* match12, const int* kp_index1, const float* level_sigma2,
+                     int nlevels, const orbm_sim3_params* params, const uint32_t* rand3, orbm_sim3_result* result,
+                     float* s12, float* R12, float* t12, orbm_pose* pose, uint8_t* inlier, orbm_sim3_hyp* hyp) {
+  int rc;
+  if (!m) return g_merr.fail(ORBX_EINVAL, "bad argument");
+  if ((rc = sim3_check(kps1, n1, kps2, n2, mps1, mps2, cam1, cam2, match12, level_sigma2, nlevels, params, rand3)))
+    return rc;
+  if (std::max(n1, n2) > m->max_kps)
+    return g_merr.fail(ORBX_ECAPACITY, "%d keypoints above the handle's max_kps %d", std::max(n1, n2), m->max_kps);
+  HIP_OK(g_merr, hipSetDevice(m->device));
+  const size_t kp = std::max(std::max(n1, n2), 1), its = params->max_iterations;
+  Stage st(m);
+  auto dk1 = st.slot<orbx_kp>(kp);
+  auto dk2 = st.slot<orbx_kp>(kp);
+  auto dn = st.slot<int>(2);
+  auto dm1 = st.slot<orbm_map_point_world>(kp);
+  auto dm2 = st.slot<orbm_map_point_world>(kp);
+  auto dc = st.slot<orbm_camera>(2);
+  auto d12 = st.slot<int>(kp);
+  auto dki = st.slot<int>(kp);
+  auto drand = st.slot<uint32_t>(3 * its);
+  auto dres = st.slot<orbm_sim3_result>(1);
+  auto dsrt = st.slot<float>(13);
+  auto dpose = st.slot<orbm_pose>(2);
+  auto din = st.slot<uint8_t>(kp);
+  auto dhyp = st.slot<orbm_sim3_hyp>(its);
+  const int counts[2] = {n1, n2};
+  const orbm_camera cams[2] = {*cam1, *cam2};
+  // s12, R12, t12, pose and hyp go up too: what the call leaves untouched comes back as it was
+  float srt[13] = {};
+  if (s12) srt[0] = *s12;
+  if (R12) std::memcpy(srt + 1, R12, 9 * sizeof(float));
+  if (t12) std::memcpy(srt + 10, t12, 3 * sizeof(float));
+  if ((rc = st.reserve()) || (rc = st.up(dk1, kps1, n1)) || (rc = st.up(dk2, kps2, n2)) ||
+      (rc = st.up(dn, counts, 2)) || (rc = st.up(dm1, mps1, n1)) || (rc = st.up(dm2, mps2, n2)) ||
+      (rc = st.up(dc, cams, 2)) || (rc = st.up(d12, match12, n1)) || (rc = st.up(dki, kp_index1, n1)) ||
+      (rc = st.up(drand, rand3, 3 * its)) || (rc = st.up(dsrt, (const float*)srt, 13)) ||
+      (rc = st.up(dpose, (const orbm_pose*)pose, 2)) || (rc = st.up(dhyp, (const orbm_sim3_hyp*)hyp, its)) ||
+      (rc = orbm_sim3_ransac_batch(m, dk1, dn, dk2, (int*)dn + 1, (int)kp, dm1, dm2, (int)kp, dc,
+                                   (orbm_camera*)dc + 1, d12, kp_index1 ? (int*)dki : nullptr, level_sigma2, nlevels,
+                                   params, drand, 1, dres, dsrt, (float*)dsrt + 1, (float*)dsrt + 10,
+                                   pose ? (orbm_pose*)dpose : nullptr, inlier ? (uint8_t*)din : nullptr,
+                                   hyp ? (orbm_sim3_hyp*)dhyp : nullptr, st.st)) ||
+      (rc = st.down(srt, dsrt, 13)) || (result && (rc = st.down(result, dres, 1))) ||
+      (pose && (rc = st.down(pose, dpose, 2))) || (inlier && (rc = st.down(inlier, din, n1))) ||
+      (hyp && (rc = st.down(hyp, dhyp, its))) || (rc = st.finish()))
+    return rc;
+  if (s12) *s12 = srt[0];
+  if (R12) std::memcpy(R12, srt + 1, 9 * sizeof(float));
+  if (t12) std::memcpy(t12, srt + 10, 3 * sizeof(float));
+  return ORBX_OK;
+}
+
 // ---------------------------------------------- pose-projection overloads
 namespace {
 
@@ -1322,32 +1483,10 @@ int orbm_prepare_pose(int mode, const orbm_camera* cam, const float* Tlw, int mo
 int orbm_prepare_sim3_match(const orbm_camera* cam1, const float* T1w, const float* T2w, float s12, const float* R12,
                             const float* t12, orbm_pose* out) {
   if (!cam1 || !T1w || !T2w || !R12 || !t12 || !out || !(s12 != 0.0f)) return g_merr.fail(ORBX_EINVAL, "bad argument");
-  // sR12 = s12*R12; sR21 = (1.0/s12)*R12.t(); t21 = -sR21*t12 (src/ORBmatcher.cc:1118-1120):
-  // scalar * Mat = convertTo(alpha) in float, -A*t = gemm small path with alpha -1
-  const float a12 = (float)(double)s12, a21 = (float)(1.0 / (double)s12);
-  float S12[12], S21[12];
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 3; ++c) {
-      S12[4 * r + c] = R12[3 * r + c] * a12 + 0.0f;
-      S21[4 * r + c] = R12[3 * c + r] * a21 + 0.0f;
-    }
-  for (int r = 0; r < 3; ++r) {
-    S12[4 * r + 3] = t12[r];
-    const float t = S21[4 * r] * t12[0] + S21[4 * r + 1] * t12[1] + S21[4 * r + 2] * t12[2];
-    S21[4 * r + 3] = (float)((double)t * -1.0 + 0.0 * 0.0);
-  }
-  for (int d = 0; d < 2; ++d) {
-    orbm_pose p{};
-    p.fx = cam1->fx;
-    p.fy = cam1->fy;
-    p.cx = cam1->cx;
-    p.cy = cam1->cy;
-    p.mbf = cam1->mbf;
-    std::memcpy(p.Rt, d == 0 ? T1w : T2w, sizeof p.Rt);
-    std::memcpy(p.Rt2, d == 0 ? S21 : S12, sizeof p.Rt2);
-    neg_rt_t(p.Rt, p.Ow);
-    out[d] = p;
-  }
+  // sR12 = s12*R12; sR21 = (1.0/s12)*R12.t(); t21 = -sR21*t12 (src/ORBmatcher.cc:1118-1120), as
+  // Sim3Solver's step 8 and its kernel compute them (orbx_sim3.cuh)
+  orbm_camera c = *cam1;
+  sim3_match_poses(c, T1w, T2w, s12, R12, t12, out);
   return ORBX_OK;
 }
 

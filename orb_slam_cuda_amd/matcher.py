@@ -28,6 +28,10 @@ for Optimizer::PoseOptimization (src/Optimizer.cc:334-543), the pose solve betwe
 
     Tcw, outlier, result = m.PoseOptimization(kps, assign, mps, inv_sigma2, cam, uright)
 
+for Sim3Solver (src/Sim3Solver.cc), loop closing's RANSAC between SearchByBoW and SearchBySim3:
+
+    (s12, R12, t12), inlier, result = m.Sim3Ransac(kps1, mps1, cam1, kps2, mps2, cam2, match12, sigma2, rand3)
+
 and for the Frame constructors' tail (src/Frame.cc:118-227, 403-463, 642-663):
 
     F = ExtractRGBD(extractor, imGray, imDepth, K, distCoef, mbf, DepthMapFactor)  # one device round trip
@@ -861,6 +865,59 @@ class ORBmatcher:
             check(lib().orbm_pose_optimization(self._h, *args), matcher=True)
         self.last_pose = pose
         return Tcw.reshape(3, 4), outlier[:n], res[0]
+
+    def Sim3Ransac(self, kps1, mps1, cam1, kps2, mps2, cam2, match12, level_sigma2, rand3=None, *, probability=0.99,
+                   min_inliers=20, max_iterations=300, fix_scale=False, first_iteration=0, best_inliers=0,
+                   kp_index1=None, want_hyp=False, host=False):
+        """Sim3Solver (src/Sim3Solver.cc): the constructor, SetRansacParameters(probability, min_inliers,
+        max_iterations) and find() in one device round trip (orbm_sim3_ransac), or on the host alone with
+        host=True (orbm_sim3_ransac_host). kps1 / kps2: KP_DTYPE (mvKeysUn); mps1 / mps2:
+        MAP_POINT_WORLD_DTYPE, one per keypoint; cam1 / cam2: _lib.camera(...) of each keyframe with its Tcw;
+        match12: int32 per keypoint of KF1, the matched keypoint of KF2 or -1; level_sigma2 = mvLevelSigma2;
+        rand3: (max_iterations, 3) uint32 raw rand() values (default: _lib.sim3_rand_fill, the C library's
+        stream). first_iteration / best_inliers resume a solver from an earlier result.
+        Returns ((s12, R12 (3, 3), t12 (3,)), inlier uint8 per keypoint of KF1, result) with result a
+        SIM3_RESULT_DTYPE record; the T12 parts are None when result['best_iteration'] < 0. The two orbm_pose
+        records for SearchBySim3 stay in self.last_sim3_poses (None likewise), the per-hypothesis records
+        (SIM3_HYP_DTYPE) in self.last_sim3_hyp with want_hyp. Entries left out for an index or octave out of
+        range set bit 512 of status() (host=True: self.last_host_status)."""
+        kps1 = np.ascontiguousarray(kps1, KP_DTYPE)
+        kps2 = np.ascontiguousarray(kps2, KP_DTYPE)
+        mps1 = np.ascontiguousarray(mps1, MAP_POINT_WORLD_DTYPE)
+        mps2 = np.ascontiguousarray(mps2, MAP_POINT_WORLD_DTYPE)
+        n1, n2 = len(kps1), len(kps2)
+        m12 = np.ascontiguousarray(match12, np.int32)
+        ki = None if kp_index1 is None else np.ascontiguousarray(kp_index1, np.int32)
+        if len(mps1) != n1 or len(mps2) != n2 or len(m12) != n1 or (ki is not None and len(ki) != n1):
+            raise _lib.OrbxError(_lib.ORBX_EINVAL, "one map point per keypoint, one match12 entry per keypoint of KF1")
+        sig = np.ascontiguousarray(level_sigma2, np.float32)
+        if rand3 is None:
+            rand3 = _lib.sim3_rand_fill(max_iterations)
+        rand3 = np.ascontiguousarray(rand3, np.uint32)
+        if rand3.size < 3 * max_iterations:
+            raise _lib.OrbxError(_lib.ORBX_EINVAL, "rand3 needs 3 values per iteration")
+        par = _lib.sim3_params(probability, min_inliers, max_iterations, fix_scale, first_iteration, best_inliers)
+        res = np.zeros(1, _lib.SIM3_RESULT_DTYPE)
+        srt = np.zeros(13, np.float32)
+        poses = np.zeros(2, _lib.POSE_DTYPE)
+        inlier = np.zeros(max(n1, 1), np.uint8)
+        hyp = np.zeros(max_iterations, _lib.SIM3_HYP_DTYPE) if want_hyp else None
+        args = (ptr(kps1), n1, ptr(kps2), n2, ptr(mps1), ptr(mps2), C.addressof(cam1), C.addressof(cam2), ptr(m12),
+                ptr(ki), ptr(sig), len(sig), ptr(par), ptr(rand3), ptr(res), ptr(srt[0:1]), ptr(srt[1:10]),
+                ptr(srt[10:13]), ptr(poses), ptr(inlier), ptr(hyp))
+        if host:
+            st = C.c_int(0)
+            check(lib().orbm_sim3_ransac_host(*args, C.byref(st)), matcher=True)
+            self.last_host_status = st.value
+        else:
+            check(lib().orbm_sim3_ransac(self._h, *args), matcher=True)
+        r = res[0]
+        self.last_sim3_hyp = hyp
+        if r["best_iteration"] < 0:
+            self.last_sim3_poses = None
+            return None, inlier[:n1], r
+        self.last_sim3_poses = poses
+        return (srt[0], srt[1:10].reshape(3, 3).copy(), srt[10:13].copy()), inlier[:n1], r
 
     def SearchByBoW(self, A: KeyFrame, B, out: list | None = None) -> int:
         """KF-Frame (B is a Frame) or KF-KF (B is a KeyFrame). Fills `out` with matched

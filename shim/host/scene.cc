@@ -14,6 +14,7 @@
 //   op 9 SearchByBoW(pKF, F, vpMapPointMatches)            Tracking.cc:842, 1465
 //   op 10 Tracking::SearchLocalPoints' body                Tracking.cc:1229-1279
 //   op 11 Optimizer::PoseOptimization(&CurrentFrame)       Tracking.cc:975, 1020
+//   op 12 Sim3Solver(pKF1, pKF2, vpMatches12, fix), SetRansacParameters, iterate(k)...  LoopClosing.cc:313-340
 // --scene-latency: the same scene rebuilt per call, only the method call on
 // the host clock (median / p99 over the calls after the warm ones).
 // Scene file: records of [u32 name length][name][u32 dtype 0 u8 / 1 i32 /
@@ -22,6 +23,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <memory>
@@ -35,6 +37,7 @@
 #include "MapPoint.h"
 #include "ORBmatcher.h"
 #include "Optimizer.h"
+#include "Sim3Solver.h"
 
 using namespace ORB_SLAM2;
 
@@ -463,6 +466,45 @@ static void run_op(const Scene& s, std::vector<int>& res, double* ms) {
           memcpy(&bits, &v, 4);
           res.push_back(bits);
         }
+      break;
+    }
+    case 12: {  // per iterate(k) call of the scene's list: [nInliers, bNoMore, T12 returned, then with a T12 its
+                // rows 0..2 as the bits of 12 floats and vbInliers...]; at the end the bits of scale, R (9), t (3)
+      auto K1 = keyframe(s, "A", pool);
+      auto K2 = keyframe(s, "B", pool);
+      observe(K1.get(), s, pool);
+      observe(K2.get(), s, pool);
+      const std::vector<MapPoint*> m12 = pointers(s, "matched", pool);
+      auto bits = [](float v) {
+        int b;
+        memcpy(&b, &v, 4);
+        return b;
+      };
+      srand((unsigned)s.i("seed"));
+      tic();
+      Sim3Solver solver(K1.get(), K2.get(), m12, s.i("fix_scale") != 0);
+      solver.SetRansacParameters((double)s.i("prob_num") / (double)s.i("prob_den"), s.i("min_inliers"),
+                                 s.i("max_iterations"));
+      for (int k : s.vec<int>("iterate")) {
+        bool bNoMore = false;
+        std::vector<bool> vbInliers;
+        int nInliers = 0;
+        const cv::Mat T12 = k < 0 ? solver.find(vbInliers, nInliers) : solver.iterate(k, bNoMore, vbInliers, nInliers);
+        res.push_back(nInliers);
+        res.push_back(bNoMore ? 1 : 0);
+        res.push_back(T12.empty() ? 0 : 1);
+        if (!T12.empty()) {
+          for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 4; ++c) res.push_back(bits(T12.at<float>(r, c)));
+          for (bool b : vbInliers) res.push_back(b ? 1 : 0);
+        }
+        if (bNoMore) break;
+      }
+      toc();
+      res.push_back(bits(solver.GetEstimatedScale()));
+      const cv::Mat R = solver.GetEstimatedRotation(), t = solver.GetEstimatedTranslation();
+      for (int k = 0; k < 9; ++k) res.push_back(bits(R.at<float>(k / 3, k % 3)));
+      for (int k = 0; k < 3; ++k) res.push_back(bits(t.at<float>(k)));
       break;
     }
     default:
