@@ -85,6 +85,9 @@
  *                          include/Optimizer.h:53, src/Optimizer.cc:334-543
  *   orbm_sim3_ransac / _batch / _host  Sim3Solver (ctor, SetRansacParameters,
  *                          iterate / find)  include/Sim3Solver.h, src/Sim3Solver.cc:37-423
+ *   orbm_create_new_map_points / _batch / _host  the loop over vMatchedIndices of
+ *                          LocalMapping::CreateNewMapPoints  src/LocalMapping.cc:317-464
+ *   orbm_compute_f12       LocalMapping::ComputeF12  src/LocalMapping.cc:572-589
  *   orbv_load_text / orbv_create  ORBVocabulary::loadFromTextFile
  *                          (DBoW2 TemplatedVocabulary, include/ORBVocabulary.h:30,
  *                          Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1338-1418)
@@ -313,7 +316,11 @@ int orbm_destroy(orbm_handle m);
  * orbm_sim3_ransac_batch / orbm_sim3_ransac treated an entry as unmatched
  * because its match12 or kp_index1 value is at or above the keyframe's
  * count, its keypoint's octave is outside [0, nlevels), or the gathered
- * list would not fit the pitch).
+ * list would not fit the pitch; bit 1024: orbm_create_new_map_points_batch /
+ * orbm_create_new_map_points rejected a match whose idx2 is at or above n2,
+ * whose keypoint's octave is outside [0, nlevels), or whose stereo keypoint
+ * has mvDepth <= 0 where UnprojectStereo needs it; bit 2048: the same calls
+ * found more new points than `capacity` and dropped the excess).
  * SearchForInitialization keeps no
  * candidate lists (8 smallest keys per query) and never sets it. Waits for
  * the matcher's own launches that may set it (on whatever streams they ran),
@@ -1390,6 +1397,154 @@ int orbm_search_for_triangulation_batch(
     const orbm_tri_pair* d_pairs, const float* scale2, const float* sigma2, int nlevels,
     int pairs, int only_stereo, int check_ori, int* d_matches12, int out_pitch,
     int* d_nmatches, void* stream);
+
+/* ------------------------------------ LocalMapping::CreateNewMapPoints
+ * The loop over vMatchedIndices (src/LocalMapping.cc:317-483) between
+ * SearchForTriangulation and the two refresh calls: the parallax test, the
+ * linear triangulation (cv::SVD::compute of a 4x4), the two
+ * KeyFrame::UnprojectStereo fallbacks (src/KeyFrame.cc:624-640) and the
+ * depth, reprojection and scale-consistency gates, in the reference's float /
+ * double arithmetic (UNPINNED). What stays with the
+ * caller is `new MapPoint`, AddObservation and AddMapPoint.
+ *
+ * LocalMapping::ComputeF12 (:572-589) from two cameras (fx, fy, cx, cy and
+ * Tcw are read): F12 row-major 3x3, for orbm_prepare_triangulation. Host
+ * only. */
+int orbm_compute_f12(const orbm_camera* cam1, const orbm_camera* cam2, float* F12);
+
+/* One keyframe pair (current keyframe = 1, neighbour pKF2 = 2) as the loop
+ * reads it: both cameras' intrinsics with invfx = 1.0f/fx as the Frame
+ * constructor makes it, mb, the CURRENT keyframe's mbf (the reference uses it
+ * for pKF2's stereo error too, :439), Tcw rows 0..2, Rwc, Twc rows 0..2 and
+ * Ow as KeyFrame::SetPose computes them, ratio_factor = 1.5f*mfScaleFactor;
+ * for the emitted observation lists the pair's keyframe indices, the
+ * descriptor-arena row of each keyframe's keypoint 0, and kf2_first: whether
+ * pKF2 precedes the current keyframe in the caller's std::map<KeyFrame*>
+ * order (that order decides which descriptor wins the refresh's ties).
+ * 376 bytes. */
+typedef struct orbm_newpt_pair {
+  float fx1, fy1, cx1, cy1, invfx1, invfy1, mb1, mbf1;
+  float fx2, fy2, cx2, cy2, invfx2, invfy2, mb2, ratio_factor;
+  float Tcw1[12], Tcw2[12];
+  float Rwc1[9], Rwc2[9];
+  float Twc1[12], Twc2[12];
+  float Ow1[3], Ow2[3];
+  uint32_t kf1, kf2, desc_base1, desc_base2;
+  int32_t kf2_first, pad;
+} orbm_newpt_pair;
+
+/* Fill *out from the two cameras (fx, fy, cx, cy, mb, mbf, Tcw) and
+ * mpCurrentKeyFrame->mfScaleFactor. Ow equals orbm_prepare_pose's. Host only. */
+int orbm_prepare_new_points(const orbm_camera* cam1, const orbm_camera* cam2, float scale_factor,
+                            uint32_t kf1, uint32_t kf2, uint32_t desc_base1, uint32_t desc_base2,
+                            int kf2_first, orbm_newpt_pair* out);
+
+/* reason[idx1]: what became of the match at idx1 */
+#define ORBM_NEWPT_NONE 0          /* matches12[idx1] < 0                                  */
+#define ORBM_NEWPT_TRIANGULATED 1  /* accepted, x3D from the SVD (:355-370)                */
+#define ORBM_NEWPT_UNPROJECT1 2    /* accepted, mpCurrentKeyFrame->UnprojectStereo(idx1)   */
+#define ORBM_NEWPT_UNPROJECT2 3    /* accepted, pKF2->UnprojectStereo(idx2)                */
+#define ORBM_NEWPT_LOW_PARALLAX 4  /* :381-382, no stereo and very low parallax            */
+#define ORBM_NEWPT_W_ZERO 5        /* x3D.at<float>(3) == 0 (:366)                         */
+#define ORBM_NEWPT_STEREO_DEPTH 6  /* UnprojectStereo of a keypoint with mvDepth <= 0: the
+                                      reference dereferences an empty Mat; status bit 1024 */
+#define ORBM_NEWPT_BEHIND1 7       /* z1 <= 0                                              */
+#define ORBM_NEWPT_BEHIND2 8       /* z2 <= 0                                              */
+#define ORBM_NEWPT_REPROJ1 9       /* reprojection error in the current keyframe           */
+#define ORBM_NEWPT_REPROJ2 10      /* reprojection error in pKF2                           */
+#define ORBM_NEWPT_DIST_ZERO 11    /* dist1 == 0 || dist2 == 0                             */
+#define ORBM_NEWPT_RATIO_LOW 12    /* ratioDist*ratioFactor < ratioOctave                  */
+#define ORBM_NEWPT_RATIO_HIGH 13   /* ratioDist > ratioOctave*ratioFactor                  */
+#define ORBM_NEWPT_DUPLICATE 14    /* accepted, but idx1 got its point from an earlier pair */
+#define ORBM_NEWPT_BAD 15          /* idx2 >= n2 or an octave outside [0, nlevels); status
+                                      bit 1024                                             */
+
+/* The loop for one pair on host arrays, without a device. Per keyframe: kps =
+ * mvKeysUn, kps_raw = mvKeys (UnprojectStereo reads the distorted keypoint;
+ * NULL = the same as kps, which holds for rectified stereo), uright = mvuRight,
+ * depth = mvDepth. level_sigma2 / scale_factors: mvLevelSigma2 /
+ * mvScaleFactors (one set, as every keyframe of a map shares them).
+ * matches12[idx1] = idx2 or -1 as orbm_search_for_triangulation writes it.
+ * pos: n1 x 3 floats, x3D where reason[idx1] is 1..3, zeros elsewhere;
+ * *nnew: the accepted matches; *status (may be NULL): 0 or 1024. */
+int orbm_create_new_map_points_host(const orbm_newpt_pair* pair, const orbx_kp* kps1, const orbx_kp* kps_raw1,
+                                    const float* uright1, const float* depth1, int n1, const orbx_kp* kps2,
+                                    const orbx_kp* kps_raw2, const float* uright2, const float* depth2, int n2,
+                                    const float* level_sigma2, const float* scale_factors, int nlevels,
+                                    const int* matches12, float* pos, uint8_t* reason, int* nnew, int* status);
+
+/* The same in one round trip through the device (synchronous). Status bit
+ * 1024 is left for orbm_get_status. */
+int orbm_create_new_map_points(orbm_handle m, const orbm_newpt_pair* pair, const orbx_kp* kps1,
+                               const orbx_kp* kps_raw1, const float* uright1, const float* depth1, int n1,
+                               const orbx_kp* kps2, const orbx_kp* kps_raw2, const float* uright2,
+                               const float* depth2, int n2, const float* level_sigma2,
+                               const float* scale_factors, int nlevels, const int* matches12, float* pos,
+                               uint8_t* reason, int* nnew);
+
+/* One accepted match, in the reference's creation order. 28 bytes. */
+typedef struct orbm_new_point {
+  float pos[3];
+  int32_t pair, idx1, idx2, kind; /* kind: ORBM_NEWPT_TRIANGULATED / UNPROJECT1 / UNPROJECT2 */
+} orbm_new_point;
+
+/* Where the batch appends its points for the calls that follow (device
+ * pointers, the struct itself is read on the host). New point k goes to row
+ * q = point_base + k of d_mps: pos, valid = 1 and obs_positive = 1 are
+ * written, the other fields stay. d_obs[2k], d_obs[2k+1]: its two
+ * observations, pKF2's first when the pair's kf2_first is set, desc_row =
+ * desc_base + idx; d_obs_off[k] = 2*min(k, nnew) for all capacity + 1
+ * entries and d_point_ids[k] = point_base + k, d_ref[k] = {kf1, kp1.octave}
+ * ({pair 0's kf1, 0} past the count) for all `capacity` slots, so
+ * orbm_refresh_map_points_batch over `capacity` points is correct without
+ * reading the count back: the slots past it have empty lists. */
+typedef struct orbm_newpt_emit {
+  orbm_map_point_world* d_mps;
+  orbm_observation* d_obs;   /* 2 * capacity */
+  uint32_t* d_obs_off;       /* capacity + 1 */
+  uint32_t* d_point_ids;     /* capacity */
+  orbm_point_refkf* d_ref;   /* capacity */
+  uint32_t point_base;
+  uint32_t pad;
+} orbm_newpt_emit;
+
+/* Batched device-resident variant, asynchronous on `stream`: `pairs` pairs
+ * with the side and pitch conventions of orbm_search_for_triangulation_batch
+ * (kp_pitch1 == 0: one current keyframe shared by every pair, d_n1 has one
+ * entry); d_kps_raw1 / d_kps_raw2 may be NULL. d_matches12 / out_pitch exactly
+ * as that call writes them; d_pairs from orbm_prepare_new_points;
+ * level_sigma2 / scale_factors are host arrays.
+ * Written: d_pos (pairs x out_pitch x 3 floats) and d_reason (pairs x
+ * out_pitch) for idx1 < n1, the tail of each row stays untouched;
+ * d_nnew_pair[p] = the matches of pair p that are accepted (after dedup);
+ * d_new[0 .. *d_nnew) = those matches of all pairs compacted in the
+ * reference's creation order (pair ascending, then idx1 ascending; found by a
+ * scan, the same order in every run), *d_nnew = their number, at most
+ * `capacity`. More than `capacity`: the excess is dropped whole (no record, no
+ * emitted row, no has_mp update; d_reason keeps its code), and status bit 2048
+ * is set. d_new may be NULL (capacity still bounds the emitted rows).
+ * dedup != 0 with a shared side 1 applies the reference's sequential rule: a
+ * keypoint idx1 accepted in several pairs keeps the lowest pair, the later
+ * ones get ORBM_NEWPT_DUPLICATE and zero positions. This equals the
+ * reference's loop, which sets the map point at idx1 before the next
+ * neighbour's search skips it, because that search runs with
+ * mbCheckOrientation = false (ORBmatcher matcher(0.6,false), :248) and its
+ * per-idx1 searches are independent (vbMatched2 is never set). With
+ * check_ori = 1 in the search the rotation histogram couples the idx1, and
+ * the equivalence does NOT hold.
+ * emit (may be NULL): see orbm_newpt_emit. d_has_mp1 / d_has_mp2 (may be
+ * NULL; laid out like the search's): set to 1 at the idx1 / idx2 of every
+ * point written, so that a following search or Fuse sees the new points.
+ * A bad entry (see ORBM_NEWPT_BAD, ORBM_NEWPT_STEREO_DEPTH) sets status bit
+ * 1024. */
+int orbm_create_new_map_points_batch(
+    orbm_handle m, const orbx_kp* d_kps1, const orbx_kp* d_kps_raw1, const float* d_uright1,
+    const float* d_depth1, const int* d_n1, int kp_pitch1, const orbx_kp* d_kps2,
+    const orbx_kp* d_kps_raw2, const float* d_uright2, const float* d_depth2, const int* d_n2,
+    int kp_pitch2, const orbm_newpt_pair* d_pairs, const float* level_sigma2,
+    const float* scale_factors, int nlevels, int pairs, const int* d_matches12, int out_pitch, int dedup,
+    float* d_pos, uint8_t* d_reason, orbm_new_point* d_new, int capacity, int* d_nnew, int* d_nnew_pair,
+    const orbm_newpt_emit* emit, uint8_t* d_has_mp1, uint8_t* d_has_mp2, void* stream);
 
 /* --------------------------------------------- device plumbing for hosts
  * Thin wrappers so a host without its own HIP binding (ctypes, cgo, JNI)

@@ -79,6 +79,12 @@ class OrbmTriPair(C.Structure):
     _fields_ = [("F12", C.c_float * 9), ("ex", C.c_float), ("ey", C.c_float)]
 
 
+class NewPtEmit(C.Structure):
+    """orbm_newpt_emit: where orbm_create_new_map_points_batch appends its points (device pointers)."""
+    _fields_ = [("d_mps", C.c_void_p), ("d_obs", C.c_void_p), ("d_obs_off", C.c_void_p), ("d_point_ids", C.c_void_p),
+                ("d_ref", C.c_void_p), ("point_base", C.c_uint32), ("pad", C.c_uint32)]
+
+
 def camera(fx, fy, cx, cy, mb, mbf, Tcw) -> OrbmCamera:
     T = np.asarray(Tcw, np.float32).reshape(-1)[:12]
     return OrbmCamera(fx, fy, cx, cy, mb, mbf, (C.c_float * 12)(*T.tolist()))
@@ -274,6 +280,19 @@ def lib() -> C.CDLL:
         L.orbm_search_for_triangulation_batch.argtypes = (
             [C.c_void_p] + ([C.c_void_p] * 9 + [C.c_int, C.c_int]) * 2 + [C.c_void_p] * 3
             + [C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p])
+        L.orbm_compute_f12.argtypes = [C.POINTER(OrbmCamera), C.POINTER(OrbmCamera), C.c_void_p]
+        L.orbm_prepare_new_points.argtypes = [C.POINTER(OrbmCamera), C.POINTER(OrbmCamera), C.c_float, C.c_uint32,
+                                              C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]
+        # pair, kps1, kps_raw1, uright1, depth1, n1, kps2, kps_raw2, uright2, depth2, n2, level_sigma2,
+        # scale_factors, nlevels, matches12, pos, reason, nnew
+        NP = ([C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+              + [C.c_void_p] * 3 + [C.POINTER(C.c_int)])
+        L.orbm_create_new_map_points_host.argtypes = NP + [C.POINTER(C.c_int)]
+        L.orbm_create_new_map_points.argtypes = [C.c_void_p] + NP
+        L.orbm_create_new_map_points_batch.argtypes = (
+            [C.c_void_p] + ([C.c_void_p] * 5 + [C.c_int]) * 2 + [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p,
+                                                                                    C.c_int, C.c_int]
+            + [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_void_p, C.POINTER(NewPtEmit)] + [C.c_void_p] * 3)
         L.orbv_last_error.restype = C.c_char_p
         L.orbv_load_text.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]
         L.orbv_create.argtypes = [C.c_int] * 5 + [C.c_void_p] * 4 + [C.c_int, C.POINTER(C.c_void_p)]
@@ -408,6 +427,56 @@ def sim3_iteration_table(probability, min_inliers, max_iterations, n_max) -> np.
     out = np.zeros(n_max + 1, np.int32)
     check(lib().orbm_sim3_iteration_table(probability, min_inliers, max_iterations, n_max, ptr(out)), matcher=True)
     return out
+
+
+# orbm_newpt_pair, orbm_new_point (include/orbx_c.h): 376 and 28 bytes
+NEWPT_PAIR_DTYPE = np.dtype(
+    [(k, "<f4") for k in ("fx1", "fy1", "cx1", "cy1", "invfx1", "invfy1", "mb1", "mbf1", "fx2", "fy2", "cx2", "cy2",
+                          "invfx2", "invfy2", "mb2", "ratio_factor")]
+    + [("Tcw1", "<f4", (12,)), ("Tcw2", "<f4", (12,)), ("Rwc1", "<f4", (9,)), ("Rwc2", "<f4", (9,)),
+       ("Twc1", "<f4", (12,)), ("Twc2", "<f4", (12,)), ("Ow1", "<f4", (3,)), ("Ow2", "<f4", (3,)), ("kf1", "<u4"),
+       ("kf2", "<u4"), ("desc_base1", "<u4"), ("desc_base2", "<u4"), ("kf2_first", "<i4"), ("pad", "<i4")])
+NEW_POINT_DTYPE = np.dtype([("pos", "<f4", (3,)), ("pair", "<i4"), ("idx1", "<i4"), ("idx2", "<i4"), ("kind", "<i4")])
+assert NEWPT_PAIR_DTYPE.itemsize == 376 and NEW_POINT_DTYPE.itemsize == 28
+STATUS_NEWPT_BAD, STATUS_NEWPT_OVERFLOW = 1024, 2048
+(NEWPT_NONE, NEWPT_TRIANGULATED, NEWPT_UNPROJECT1, NEWPT_UNPROJECT2, NEWPT_LOW_PARALLAX, NEWPT_W_ZERO,
+ NEWPT_STEREO_DEPTH, NEWPT_BEHIND1, NEWPT_BEHIND2, NEWPT_REPROJ1, NEWPT_REPROJ2, NEWPT_DIST_ZERO, NEWPT_RATIO_LOW,
+ NEWPT_RATIO_HIGH, NEWPT_DUPLICATE, NEWPT_BAD) = range(16)
+
+
+def compute_f12(cam1: OrbmCamera, cam2: OrbmCamera) -> np.ndarray:
+    """LocalMapping::ComputeF12 of two cameras (orbm_compute_f12), 3x3 float32."""
+    F = np.zeros((3, 3), np.float32)
+    check(lib().orbm_compute_f12(C.byref(cam1), C.byref(cam2), ptr(F)), matcher=True)
+    return F
+
+
+def prepare_new_points(cam1: OrbmCamera, cam2: OrbmCamera, scale_factor: float, kf1=0, kf2=1, desc_base1=0,
+                       desc_base2=0, kf2_first=False) -> np.ndarray:
+    """One orbm_newpt_pair record (orbm_prepare_new_points)."""
+    out = np.zeros(1, NEWPT_PAIR_DTYPE)
+    check(lib().orbm_prepare_new_points(C.byref(cam1), C.byref(cam2), scale_factor, kf1, kf2, desc_base1, desc_base2,
+                                        int(bool(kf2_first)), ptr(out)), matcher=True)
+    return out
+
+
+def create_new_map_points_host(pair, kps1, uright1, depth1, kps2, uright2, depth2, level_sigma2, scale_factors,
+                               matches12, kps_raw1=None, kps_raw2=None):
+    """orbm_create_new_map_points_host: (pos (n1, 3), reason (n1,), nnew, status), no device."""
+    n1, n2 = len(kps1), len(kps2)
+    f = lambda a: np.ascontiguousarray(a, np.float32)  # noqa: E731
+    kps1, kps2 = np.ascontiguousarray(kps1, KP_DTYPE), np.ascontiguousarray(kps2, KP_DTYPE)
+    r1 = None if kps_raw1 is None else np.ascontiguousarray(kps_raw1, KP_DTYPE)
+    r2 = None if kps_raw2 is None else np.ascontiguousarray(kps_raw2, KP_DTYPE)
+    u1, d1, u2, d2, s2, sf = f(uright1), f(depth1), f(uright2), f(depth2), f(level_sigma2), f(scale_factors)
+    m12 = np.ascontiguousarray(matches12, np.int32)
+    assert len(u1) == n1 and len(d1) == n1 and len(m12) == n1 and len(u2) == n2 and len(d2) == n2
+    pos, reason = np.zeros((n1, 3), np.float32), np.zeros(n1, np.uint8)
+    nnew, st = C.c_int(0), C.c_int(0)
+    check(lib().orbm_create_new_map_points_host(ptr(pair), ptr(kps1), ptr(r1), ptr(u1), ptr(d1), n1, ptr(kps2),
+                                                ptr(r2), ptr(u2), ptr(d2), n2, ptr(s2), ptr(sf), len(s2), ptr(m12),
+                                                ptr(pos), ptr(reason), C.byref(nnew), C.byref(st)), matcher=True)
+    return pos, reason, nnew.value, st.value
 
 
 OBSERVATION_DTYPE = np.dtype([("kf", "<u4"), ("desc_row", "<u4")])

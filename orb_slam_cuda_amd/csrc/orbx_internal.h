@@ -447,6 +447,39 @@ struct TriParams {
 };
 int launch_search_tri(const TriParams& P, const TriSide& A, const TriSide& B, const orbm_tri_pair* pairs, int npairs,
                       int* matches12, int* nmatches, void* stream);
+// orbx_newpoints.hip — LocalMapping::CreateNewMapPoints' loop over the search's
+// pairs: one lane per (pair, idx1), then the first-pair rule and the ordered
+// compaction (the arithmetic and status bits 1024 / 2048 are in orbx_newpoints.cuh)
+struct NewPtArgs {  // passed to the kernels by value
+  const orbx_kp *kps1, *raw1;  // raw: mvKeys, or null for "the same as kps"
+  const float *ur1, *dp1;
+  const int* n1;
+  int kp_pitch1;  // 0: one keyframe shared by every pair
+  const orbx_kp *kps2, *raw2;
+  const float *ur2, *dp2;
+  const int* n2;
+  int kp_pitch2;
+  float sigma2[kMaxLevels], scale[kMaxLevels];  // mvLevelSigma2, mvScaleFactors
+  int nlevels, npairs;
+  const int* matches12;
+  int out_pitch, dedup;
+  float* pos;
+  uint8_t* reason;
+  orbm_new_point* out_new;  // or null
+  int capacity;
+  int *nnew, *nnew_pair;
+  orbm_newpt_emit emit;  // read when has_emit
+  int has_emit;
+  uint8_t *has_mp1, *has_mp2;  // or null
+  int* err;                    // the handle's status word
+};
+// hipSuccess (0) or the launch's hipError_t
+int launch_new_points(const NewPtArgs& A, const orbm_newpt_pair* d_pairs, void* stream);
+int create_new_map_points_host(const orbm_newpt_pair& P, const orbx_kp* kps1, const orbx_kp* raw1, const float* ur1,
+                               const float* dp1, int n1, const orbx_kp* kps2, const orbx_kp* raw2, const float* ur2,
+                               const float* dp2, int n2, const float* sigma2, const float* scale, int nlevels,
+                               const int* matches12, float* pos, uint8_t* reason, int* nnew, int* status);
+void compute_f12_host(const orbm_camera& c1, const orbm_camera& c2, float* F12);
 // Stream order of a handle's device workspace: a launch that uses it first
 // waits for the last launch that used it (on whatever stream that was), so
 // calls of one handle on different streams never overlap on its scratch.

@@ -3,7 +3,7 @@
 // host-array entry points staged through the handle's arena. The kernels are in
 // orbx_top2.hip, orbx_bow.hip, orbx_init.hip, orbx_stereo.hip,
 // orbx_project.hip, orbx_project_pose.hip, orbx_frustum.hip,
-// orbx_triangulate.hip, orbx_mappoint.hip, orbx_poseopt.hip and orbx_sim3.hip.
+// orbx_triangulate.hip, orbx_mappoint.hip, orbx_poseopt.hip, orbx_sim3.hip and orbx_newpoints.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -19,6 +19,7 @@
 #include "orbx_hostutil.h"
 #include "orbx_internal.h"
 #include "orbx_mappoint.cuh"
+#include "orbx_newpoints.cuh"
 #include "orbx_posemath.cuh"
 #include "orbx_poseopt.cuh"
 #include "orbx_sim3.cuh"
@@ -1427,6 +1428,153 @@ int orbm_sim3_ransac(orbm_handle m, const orbx_kp* kps1, int n1, const orbx_kp* 
   if (s12) *s12 = srt[0];
   if (R12) std::memcpy(R12, srt + 1, 9 * sizeof(float));
   if (t12) std::memcpy(t12, srt + 10, 3 * sizeof(float));
+  return ORBX_OK;
+}
+
+// ------------------------------------- LocalMapping::CreateNewMapPoints
+int orbm_compute_f12(const orbm_camera* cam1, const orbm_camera* cam2, float* F12) {
+  if (!cam1 || !cam2 || !F12) return g_merr.fail(ORBX_EINVAL, "bad argument");
+  compute_f12_host(*cam1, *cam2, F12);
+  return ORBX_OK;
+}
+
+int orbm_prepare_new_points(const orbm_camera* cam1, const orbm_camera* cam2, float scale_factor, uint32_t kf1,
+                            uint32_t kf2, uint32_t desc_base1, uint32_t desc_base2, int kf2_first,
+                            orbm_newpt_pair* out) {
+  if (!cam1 || !cam2 || !out) return g_merr.fail(ORBX_EINVAL, "bad argument");
+  newpt_prepare(*cam1, *cam2, scale_factor, kf1, kf2, desc_base1, desc_base2, kf2_first, out);
+  return ORBX_OK;
+}
+
+namespace {
+int newpt_check(const orbm_newpt_pair* pair, const orbx_kp* kps1, const float* uright1, const float* depth1, int n1,
+                const orbx_kp* kps2, const float* uright2, const float* depth2, int n2, const float* level_sigma2,
+                const float* scale_factors, int nlevels, const int* matches12, float* pos, uint8_t* reason) {
+  if (!pair || n1 < 0 || n2 < 0 || !level_sigma2 || !scale_factors || nlevels < 1 || nlevels > kMaxLevels)
+    return g_merr.fail(ORBX_EINVAL, "bad argument");
+  if (n1 && (!kps1 || !uright1 || !depth1 || !matches12 || !pos || !reason))
+    return g_merr.fail(ORBX_EINVAL, "null array");
+  if (n2 && (!kps2 || !uright2 || !depth2)) return g_merr.fail(ORBX_EINVAL, "null array");
+  return ORBX_OK;
+}
+}  // namespace
+
+int orbm_create_new_map_points_host(const orbm_newpt_pair* pair, const orbx_kp* kps1, const orbx_kp* kps_raw1,
+                                    const float* uright1, const float* depth1, int n1, const orbx_kp* kps2,
+                                    const orbx_kp* kps_raw2, const float* uright2, const float* depth2, int n2,
+                                    const float* level_sigma2, const float* scale_factors, int nlevels,
+                                    const int* matches12, float* pos, uint8_t* reason, int* nnew, int* status) {
+  int rc;
+  if ((rc = newpt_check(pair, kps1, uright1, depth1, n1, kps2, uright2, depth2, n2, level_sigma2, scale_factors,
+                        nlevels, matches12, pos, reason)))
+    return rc;
+  return create_new_map_points_host(*pair, kps1, kps_raw1, uright1, depth1, n1, kps2, kps_raw2, uright2, depth2, n2,
+                                    level_sigma2, scale_factors, nlevels, matches12, pos, reason, nnew, status);
+}
+
+int orbm_create_new_map_points_batch(orbm_handle m, const orbx_kp* d_kps1, const orbx_kp* d_kps_raw1,
+                                     const float* d_uright1, const float* d_depth1, const int* d_n1, int kp_pitch1,
+                                     const orbx_kp* d_kps2, const orbx_kp* d_kps_raw2, const float* d_uright2,
+                                     const float* d_depth2, const int* d_n2, int kp_pitch2,
+                                     const orbm_newpt_pair* d_pairs, const float* level_sigma2,
+                                     const float* scale_factors, int nlevels, int pairs, const int* d_matches12,
+                                     int out_pitch, int dedup, float* d_pos, uint8_t* d_reason, orbm_new_point* d_new,
+                                     int capacity, int* d_nnew, int* d_nnew_pair, const orbm_newpt_emit* emit,
+                                     uint8_t* d_has_mp1, uint8_t* d_has_mp2, void* stream) {
+  if (!m || !d_kps1 || !d_uright1 || !d_depth1 || !d_n1 || !d_kps2 || !d_uright2 || !d_depth2 || !d_n2 || !d_pairs ||
+      !level_sigma2 || !scale_factors || !d_matches12 || !d_pos || !d_reason || !d_nnew || !d_nnew_pair ||
+      pairs < 1 || kp_pitch1 < 0 || kp_pitch2 < 1 || out_pitch < 1 || capacity < 0 || nlevels < 1 ||
+      nlevels > kMaxLevels)
+    return g_merr.fail(ORBX_EINVAL, "bad argument");
+  if (emit && (!emit->d_mps || !emit->d_obs || !emit->d_obs_off || !emit->d_point_ids || !emit->d_ref))
+    return g_merr.fail(ORBX_EINVAL, "the emit arguments need all five arrays");
+  HIP_OK(g_merr, hipSetDevice(m->device));
+  hipStream_t s = (hipStream_t)stream;
+  NewPtArgs A{};
+  A.kps1 = d_kps1;
+  A.raw1 = d_kps_raw1;
+  A.ur1 = d_uright1;
+  A.dp1 = d_depth1;
+  A.n1 = d_n1;
+  A.kp_pitch1 = kp_pitch1;
+  A.kps2 = d_kps2;
+  A.raw2 = d_kps_raw2;
+  A.ur2 = d_uright2;
+  A.dp2 = d_depth2;
+  A.n2 = d_n2;
+  A.kp_pitch2 = kp_pitch2;
+  std::memcpy(A.sigma2, level_sigma2, (size_t)nlevels * sizeof(float));
+  std::memcpy(A.scale, scale_factors, (size_t)nlevels * sizeof(float));
+  A.nlevels = nlevels;
+  A.npairs = pairs;
+  A.matches12 = d_matches12;
+  A.out_pitch = out_pitch;
+  A.dedup = dedup;
+  A.pos = d_pos;
+  A.reason = d_reason;
+  A.out_new = d_new;
+  A.capacity = capacity;
+  A.nnew = d_nnew;
+  A.nnew_pair = d_nnew_pair;
+  if (emit) A.emit = *emit;
+  A.has_emit = emit ? 1 : 0;
+  A.has_mp1 = d_has_mp1;
+  A.has_mp2 = d_has_mp2;
+  A.err = m->err.as<int>();
+  if (const int e = launch_new_points(A, d_pairs, stream))
+    return g_merr.fail(ORBX_EDEVICE, "CreateNewMapPoints launch: %s", hipGetErrorString((hipError_t)e));
+  if (m->errm.mark(s)) return g_merr.fail(ORBX_EDEVICE, "event record failed");
+  return ORBX_OK;
+}
+
+int orbm_create_new_map_points(orbm_handle m, const orbm_newpt_pair* pair, const orbx_kp* kps1,
+                               const orbx_kp* kps_raw1, const float* uright1, const float* depth1, int n1,
+                               const orbx_kp* kps2, const orbx_kp* kps_raw2, const float* uright2,
+                               const float* depth2, int n2, const float* level_sigma2, const float* scale_factors,
+                               int nlevels, const int* matches12, float* pos, uint8_t* reason, int* nnew) {
+  int rc;
+  if (!m) return g_merr.fail(ORBX_EINVAL, "bad argument");
+  if ((rc = newpt_check(pair, kps1, uright1, depth1, n1, kps2, uright2, depth2, n2, level_sigma2, scale_factors,
+                        nlevels, matches12, pos, reason)))
+    return rc;
+  if (n1 == 0) {
+    if (nnew) *nnew = 0;
+    return ORBX_OK;
+  }
+  HIP_OK(g_merr, hipSetDevice(m->device));
+  const size_t a = n1, b = std::max(n2, 1);
+  Stage st(m);
+  auto dk1 = st.slot<orbx_kp>(a);
+  auto dr1 = st.slot<orbx_kp>(a);
+  auto du1 = st.slot<float>(a);
+  auto dd1 = st.slot<float>(a);
+  auto dk2 = st.slot<orbx_kp>(b);
+  auto dr2 = st.slot<orbx_kp>(b);
+  auto du2 = st.slot<float>(b);
+  auto dd2 = st.slot<float>(b);
+  auto dn = st.slot<int>(4);  // n1, n2, nnew, nnew_pair
+  auto dp = st.slot<orbm_newpt_pair>(1);
+  auto dm = st.slot<int>(a);
+  auto dpos = st.slot<float>(3 * a);
+  auto dre = st.slot<uint8_t>(a);
+  const int counts[2] = {n1, n2};
+  int total = 0;
+  if ((rc = st.reserve()) || (rc = st.up(dk1, kps1, n1)) || (rc = st.up(dr1, kps_raw1, n1)) ||
+      (rc = st.up(du1, uright1, n1)) || (rc = st.up(dd1, depth1, n1)) || (rc = st.up(dk2, kps2, n2)) ||
+      (rc = st.up(dr2, kps_raw2, n2)) || (rc = st.up(du2, uright2, n2)) || (rc = st.up(dd2, depth2, n2)) ||
+      (rc = st.up(dn, counts, 2)) || (rc = st.up(dp, pair, 1)) || (rc = st.up(dm, matches12, n1)) ||
+      (rc = orbm_create_new_map_points_batch(m, dk1, kps_raw1 ? (orbx_kp*)dr1 : nullptr, du1, dd1, dn, (int)a, dk2,
+                                             kps_raw2 ? (orbx_kp*)dr2 : nullptr, du2, dd2, (int*)dn + 1, (int)b, dp,
+                                             level_sigma2, scale_factors, nlevels, 1, dm, (int)a, 0, dpos, dre,
+                                             nullptr, n1, (int*)dn + 2, (int*)dn + 3, nullptr, nullptr, nullptr,
+                                             st.st)) ||
+      (rc = st.down(pos, dpos, 3 * a)) || (rc = st.down(reason, dre, a)) ||
+      (rc = hipMemcpyAsync(&total, (int*)dn + 2, sizeof(int), hipMemcpyDeviceToHost, st.st) == hipSuccess
+                ? ORBX_OK
+                : g_merr.fail(ORBX_EDEVICE, "count read-back failed")) ||
+      (rc = st.finish()))
+    return rc;
+  if (nnew) *nnew = total;
   return ORBX_OK;
 }
 

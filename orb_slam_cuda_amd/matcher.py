@@ -387,6 +387,9 @@ class KeyFrame:
     mbf: float = 0.0
     mvLevelSigma2: np.ndarray | None = None
     mvInvLevelSigma2: np.ndarray | None = None
+    mvDepth: np.ndarray | None = None      # (N,) float32, -1 = monocular (CreateNewMapPoints)
+    mb: float = 0.0
+    mvKeys: np.ndarray | None = None       # the distorted keypoints; None = the same as mvKeysUn
     mBowVec: dict = field(default_factory=dict)   # {WordId: value} (ComputeBoW); read by KeyFrameDatabase
     mnId: int = 0
 
@@ -918,6 +921,63 @@ class ORBmatcher:
             return None, inlier[:n1], r
         self.last_sim3_poses = poses
         return (srt[0], srt[1:10].reshape(3, 3).copy(), srt[10:13].copy()), inlier[:n1], r
+
+    def CreateNewMapPoints(self, pKF1: KeyFrame, neighbours, matches12=None, *, host=False):
+        """LocalMapping::CreateNewMapPoints' loop (src/LocalMapping.cc:270-484) for the current keyframe pKF1
+        against `neighbours` (KeyFrames, in GetBestCovisibilityKeyFrames order; the baseline test of :277-294
+        is the caller's): per neighbour ComputeF12 (orbm_compute_f12), SearchForTriangulation(pKF1, pKF2, F12,
+        ., false) and the triangulation of its matches (orbm_create_new_map_points, or with host=True
+        orbm_create_new_map_points_host). A point accepted at idx1 sets pKF1's and pKF2's map point flags
+        before the next search, as the reference's AddMapPoint does (mvpMapPoints must be masks).
+        matches12: one int32 array per neighbour to use instead of the searches.
+        Returns (points, reasons): points a list of (neighbour, idx1, idx2, x3D (3,) float32, kind) in creation
+        order for the caller's `new MapPoint` loop, reasons one uint8 array (_lib.NEWPT_*) per neighbour.
+        Rejected entries with an index, octave or stereo depth out of range set bit 1024 of status()."""
+        def side(K):
+            n = K.N
+            ur = np.full(n, -1, np.float32) if K.mvuRight is None else np.ascontiguousarray(K.mvuRight, np.float32)
+            dp = np.full(n, -1, np.float32) if K.mvDepth is None else np.ascontiguousarray(K.mvDepth, np.float32)
+            raw = None if K.mvKeys is None else np.ascontiguousarray(K.mvKeys, KP_DTYPE)
+            cam = _lib.camera(K.fx, K.fy, K.cx, K.cy, K.mb, K.mbf, np.asarray(K.mTcw, np.float32)[:3])
+            return np.ascontiguousarray(K.mvKeysUn, KP_DTYPE), raw, ur, dp, cam
+        k1, r1, u1, d1, cam1 = side(pKF1)
+        sig = np.ascontiguousarray(pKF1.mvLevelSigma2, np.float32)
+        sf = np.ascontiguousarray(pKF1.mvScaleFactors, np.float32)
+        points, reasons = [], []
+        for p, pKF2 in enumerate(neighbours):
+            k2, r2, u2, d2, cam2 = side(pKF2)
+            if matches12 is None:
+                F12 = _lib.compute_f12(cam1, cam2)
+                saved = self.mbCheckOrientation
+                self.mbCheckOrientation = False  # ORBmatcher matcher(0.6,false) (:248)
+                try:
+                    self.SearchForTriangulation(pKF1, pKF2, F12, None, False)
+                finally:
+                    self.mbCheckOrientation = saved
+                m12 = self.last_matches
+            else:
+                m12 = np.ascontiguousarray(matches12[p], np.int32)
+            pair = _lib.prepare_new_points(cam1, cam2, pKF1.mfScaleFactor, 0, p + 1)
+            if host:
+                pos, reason, _, st = _lib.create_new_map_points_host(pair, k1, u1, d1, k2, u2, d2, sig, sf, m12, r1, r2)
+                self.last_host_status = st
+            else:
+                n1 = len(k1)
+                pos, reason = np.zeros((max(n1, 1), 3), np.float32), np.zeros(max(n1, 1), np.uint8)
+                nnew = C.c_int(0)
+                check(lib().orbm_create_new_map_points(
+                    self._h, ptr(pair), ptr(k1), ptr(r1), ptr(u1), ptr(d1), n1, ptr(k2), ptr(r2), ptr(u2), ptr(d2),
+                    len(k2), ptr(sig), ptr(sf), len(sig), ptr(m12), ptr(pos), ptr(reason), C.byref(nnew)),
+                    matcher=True)
+                pos, reason = pos[:n1], reason[:n1]
+            for i in np.nonzero((reason >= _lib.NEWPT_TRIANGULATED) & (reason <= _lib.NEWPT_UNPROJECT2))[0]:
+                points.append((p, int(i), int(m12[i]), pos[i].copy(), int(reason[i])))
+                if np.asarray(pKF1.mvpMapPoints).dtype in (np.bool_, np.uint8):
+                    pKF1.mvpMapPoints[i] = 1
+                if np.asarray(pKF2.mvpMapPoints).dtype in (np.bool_, np.uint8):
+                    pKF2.mvpMapPoints[m12[i]] = 1
+            reasons.append(reason)
+        return points, reasons
 
     def SearchByBoW(self, A: KeyFrame, B, out: list | None = None) -> int:
         """KF-Frame (B is a Frame) or KF-KF (B is a KeyFrame). Fills `out` with matched

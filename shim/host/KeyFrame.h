@@ -1,6 +1,6 @@
 // The slice of ORB_SLAM2::KeyFrame (include/KeyFrame.h) the matcher shim
 // reads and Fuse mutates: camera (fx .. mb, KeyFrame.h:161), keypoints,
-// mvuRight, descriptors, mFeatVec, scale tables and image bounds
+// mvuRight, mvDepth, descriptors, mFeatVec, scale tables and image bounds
 // (KeyFrame.h:165-192), the pose (GetPose / GetRotation / GetTranslation /
 // GetCameraCenter, src/KeyFrame.cc:77-122) and the MapPoint matches
 // (GetMapPointMatches / GetMapPoints / GetMapPoint / AddMapPoint /
@@ -21,12 +21,13 @@ class KeyFrame {
   KeyFrame() : Tcw(4, 4, CV_32F) { set_identity(); }
   explicit KeyFrame(const Frame& F)
       : fx(F.fx), fy(F.fy), cx(F.cx), cy(F.cy), invfx(F.invfx), invfy(F.invfy), mbf(F.mbf), mb(F.mb), N(F.N),
-        mvKeys(F.mvKeys), mvKeysUn(F.mvKeysUn), mvuRight(F.mvuRight), mDescriptors(F.mDescriptors.clone()),
+        mvKeys(F.mvKeys), mvKeysUn(F.mvKeysUn), mvuRight(F.mvuRight), mvDepth(F.mvDepth), mDescriptors(F.mDescriptors.clone()),
         mFeatVec(F.mFeatVec), mnScaleLevels(F.mnScaleLevels), mfScaleFactor(F.mfScaleFactor),
         mfLogScaleFactor(F.mfLogScaleFactor), mvScaleFactors(F.mvScaleFactors), mvLevelSigma2(F.mvLevelSigma2),
         mvInvLevelSigma2(F.mvInvLevelSigma2), mnMinX((int)F.mnMinX), mnMinY((int)F.mnMinY), mnMaxX((int)F.mnMaxX),
         mnMaxY((int)F.mnMaxY), Tcw(4, 4, CV_32F), mvpMapPoints(F.mvpMapPoints) {
     if (mvuRight.empty()) mvuRight.assign(N, -1.0f);
+    if (mvDepth.empty()) mvDepth.assign(N, -1.0f);
     if (!F.mTcw.empty()) SetPose(F.mTcw);
     else set_identity();
   }
@@ -63,7 +64,7 @@ class KeyFrame {
   float fx = 0, fy = 0, cx = 0, cy = 0, invfx = 0, invfy = 0, mbf = 0, mb = 0;
   int N = 0;
   std::vector<cv::KeyPoint> mvKeys, mvKeysUn;
-  std::vector<float> mvuRight;
+  std::vector<float> mvuRight, mvDepth;  // mvDepth: UnprojectStereo and CreateNewMapPoints' stereo parallax
   cv::Mat mDescriptors;
   DBoW2::FeatureVector mFeatVec;
   int mnScaleLevels = 8;

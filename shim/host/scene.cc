@@ -15,6 +15,7 @@
 //   op 10 Tracking::SearchLocalPoints' body                Tracking.cc:1229-1279
 //   op 11 Optimizer::PoseOptimization(&CurrentFrame)       Tracking.cc:975, 1020
 //   op 12 Sim3Solver(pKF1, pKF2, vpMatches12, fix), SetRansacParameters, iterate(k)...  LoopClosing.cc:313-340
+//   op 13 CreateNewMapPoints(pKF, vpNeighKFs, bMonocular): the search, triangulation and refresh of LocalMapping.cc:270-483
 // --scene-latency: the same scene rebuilt per call, only the method call on
 // the host clock (median / p99 over the calls after the warm ones).
 // Scene file: records of [u32 name length][name][u32 dtype 0 u8 / 1 i32 /
@@ -25,6 +26,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <set>
@@ -34,6 +36,7 @@
 
 #include "Frame.h"
 #include "KeyFrame.h"
+#include "LocalMapping.h"
 #include "MapPoint.h"
 #include "ORBmatcher.h"
 #include "Optimizer.h"
@@ -192,6 +195,8 @@ std::unique_ptr<KeyFrame> keyframe(const Scene& s, const std::string& X,
   std::unique_ptr<KeyFrame> K(new KeyFrame());
   fill_common(s, X, *K);
   if (K->mvuRight.empty()) K->mvuRight.assign(K->N, -1.0f);
+  if (s.has(X + "_depth")) K->mvDepth = s.vec<float>(X + "_depth");
+  else K->mvDepth.assign(K->N, -1.0f);
   const auto cam = s.vec<float>(X + "_cam");
   K->fx = cam[0];
   K->fy = cam[1];
@@ -505,6 +510,44 @@ static void run_op(const Scene& s, std::vector<int>& res, double* ms) {
       const cv::Mat R = solver.GetEstimatedRotation(), t = solver.GetEstimatedTranslation();
       for (int k = 0; k < 9; ++k) res.push_back(bits(R.at<float>(k / 3, k % 3)));
       for (int k = 0; k < 3; ++k) res.push_back(bits(t.at<float>(k)));
+      break;
+    }
+    case 13: {  // -> [n, per new point: neighbour, idx1, idx2, kind, pKF2 precedes pKF1 in std::map order, the bits of
+                // x3D (3), normal (3), min / max distance, the descriptor as 8 words]
+      auto K1 = keyframe(s, "A", pool);
+      std::vector<std::unique_ptr<KeyFrame>> owned;
+      std::vector<KeyFrame*> neigh;
+      for (int p = 0; p < s.i("neighbours"); ++p) {
+        owned.push_back(keyframe(s, "B" + std::to_string(p), pool));
+        neigh.push_back(owned.back().get());
+      }
+      tic();
+      const std::vector<NewMapPoint> pts = CreateNewMapPoints(K1.get(), neigh, s.i("mono") != 0);
+      toc();
+      auto bits = [](float v) {
+        int b;
+        memcpy(&b, &v, 4);
+        return b;
+      };
+      res.push_back((int)pts.size());
+      for (const NewMapPoint& q : pts) {
+        int p = 0;
+        while (neigh[p] != q.pKF2) ++p;
+        res.push_back(p);
+        res.push_back((int)q.idx1);
+        res.push_back((int)q.idx2);
+        res.push_back(q.kind);
+        res.push_back(std::less<KeyFrame*>()(q.pKF2, K1.get()) ? 1 : 0);
+        for (int k = 0; k < 3; ++k) res.push_back(bits(q.x3D.at<float>(k)));
+        for (int k = 0; k < 3; ++k) res.push_back(bits(q.normal.at<float>(k)));
+        res.push_back(bits(q.minDistance));
+        res.push_back(bits(q.maxDistance));
+        for (int k = 0; k < 8; ++k) {
+          int w;
+          memcpy(&w, q.descriptor.data + 4 * k, 4);
+          res.push_back(w);
+        }
+      }
       break;
     }
     default:
