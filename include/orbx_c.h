@@ -88,6 +88,9 @@
  *   orbm_create_new_map_points / _batch / _host  the loop over vMatchedIndices of
  *                          LocalMapping::CreateNewMapPoints  src/LocalMapping.cc:317-464
  *   orbm_compute_f12       LocalMapping::ComputeF12  src/LocalMapping.cc:572-589
+ *   orbm_initialize / _batch / _host  Initializer::Initialize and everything under
+ *                          it  include/Initializer.h, src/Initializer.cc:44-929
+ *                          (Tracking::MonocularInitialization src/Tracking.cc:638-700)
  *   orbv_load_text / orbv_create  ORBVocabulary::loadFromTextFile
  *                          (DBoW2 TemplatedVocabulary, include/ORBVocabulary.h:30,
  *                          Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1338-1418)
@@ -320,7 +323,9 @@ int orbm_destroy(orbm_handle m);
  * orbm_create_new_map_points rejected a match whose idx2 is at or above n2,
  * whose keypoint's octave is outside [0, nlevels), or whose stereo keypoint
  * has mvDepth <= 0 where UnprojectStereo needs it; bit 2048: the same calls
- * found more new points than `capacity` and dropped the excess).
+ * found more new points than `capacity` and dropped the excess; bit 4096:
+ * orbm_initialize_batch / orbm_initialize left a match out whose matches12
+ * value is at or above n2).
  * SearchForInitialization keeps no
  * candidate lists (8 smallest keys per query) and never sets it. Waits for
  * the matcher's own launches that may set it (on whatever streams they ran),
@@ -944,6 +949,131 @@ int orbm_sim3_ransac_batch(orbm_handle m, const orbx_kp* d_kps1, const int* d_n1
                            int pairs, orbm_sim3_result* d_result, float* d_s12, float* d_R12,
                            float* d_t12, orbm_pose* d_pose, uint8_t* d_inlier, orbm_sim3_hyp* d_hyp,
                            void* stream);
+
+/* ------------------------------------------------------------ Initializer
+ * The monocular bootstrap between SearchForInitialization and
+ * CreateInitialMapMonocular (src/Tracking.cc:638-700): Initializer::Initialize
+ * (src/Initializer.cc:44-121) with the draws (:82-97), FindHomography (:124-172),
+ * FindFundamental (:175-223), Normalize (:749-795), ComputeH21 / ComputeF21
+ * (:226-303), CheckHomography / CheckFundamental (:305-468), ReconstructF
+ * (:470-570), ReconstructH (:572-732), Triangulate (:734-747), CheckRT
+ * (:798-907) and DecomposeE (:909-929) as one call.
+ *
+ * Inputs per pair: kps1 / kps2 = mvKeysUn of the reference and the current
+ * frame (only x, y are read), n1 / n2 their counts; matches12[i1] = the index
+ * in frame 2, or negative (what orbm_search_for_initialization[_batch] writes,
+ * at the same pitch; the call counts the matches itself). The gathered list
+ * (i1, matches12[i1]) keeps the order of i1; N is its length. A matches12
+ * value >= n2 leaves the entry out and sets status bit 4096. cam: fx, fy, cx,
+ * cy are read. rand8[max_iterations][8]: the raw rand() values of the eight
+ * draws of each iteration (orbm_initializer_rand_fill), not indices: the call
+ * applies DUtils::Random::RandomInt and the swap-with-back draw itself, on
+ * the N it finds.
+ *
+ * Outputs (each may be NULL): *result below; R21[9] (row-major), t21[3], Tcw[12]
+ * = [R21 | t21], written when result.ok; p3d[n1][3] = vP3D and triangulated[n1]
+ * = vbTriangulated of the winning reconstruction when result.ok, zeros
+ * otherwise; matches12_out[i1] = matches12[i1] where that is negative or the
+ * entry is triangulated, else -1 (src/Tracking.cc:688-693); inlier_h[k] /
+ * inlier_f[k] for k < N = vbMatchesInliers of the best homography / fundamental
+ * matrix (zeros when there is none); T1[9], T2[9] of Normalize; H21[9], F21[9]
+ * the best of each (written when result.best_h / best_f >= 0); hyp[h] =
+ * homography hypothesis h, hyp[max_iterations + h] = fundamental hypothesis h,
+ * for h < max_iterations; rt[8] = the candidate (R, t) of the reconstruction
+ * that ran (4 for F, 8 for H, the rest zero; written when a model was chosen).
+ * With N < 8 (undefined in the reference) only *result is written: ok = 0, code
+ * = ORBM_INIT_TOO_FEW_MATCHES, n = N. */
+#define ORBM_INIT_TOO_FEW_MATCHES 1 /* N < 8 */
+#define ORBM_INIT_NO_SCORE 2        /* SH and SF both zero: the reference would pass an empty F on */
+#define ORBM_INIT_DEGENERATE 3      /* ReconstructH: d1/d2 or d2/d3 < 1.00001 (:597) */
+#define ORBM_INIT_NO_CLEAR_WINNER 4 /* nsimilar > 1 (:517); secondBestGood >= 0.75*bestGood (:721) */
+#define ORBM_INIT_TOO_FEW_POINTS 5  /* maxGood < nMinGood (:517); bestGood <= minTriangulated or 0.9*N (:721) */
+#define ORBM_INIT_LOW_PARALLAX 6    /* :525-567, :721 */
+#define ORBM_INIT_ACCEPTED 7
+#define ORBM_INIT_MODEL_H 1
+#define ORBM_INIT_MODEL_F 2
+
+typedef struct orbm_init_params {
+  float sigma;              /* Initializer(ReferenceFrame, sigma = 1.0, iterations = 200) */
+  int32_t max_iterations;   /* 1 .. 1024 (orbm_initializer_limits) */
+  float min_parallax;       /* 1.0 (:116, :118) */
+  int32_t min_triangulated; /* 50 */
+} orbm_init_params; /* 16 B */
+
+typedef struct orbm_init_result {
+  int32_t ok;         /* Initialize's return value */
+  int32_t code;       /* ORBM_INIT_* */
+  int32_t n;          /* N */
+  int32_t model;      /* 0, ORBM_INIT_MODEL_H or ORBM_INIT_MODEL_F */
+  float SH, SF, RH;
+  int32_t best_h;     /* the iteration whose homography was kept, -1: none scored above 0 */
+  int32_t best_f;
+  int32_t best_rt;    /* the candidate the acceptance rule looked at (maxGood's / bestSolutionIdx), -1: none */
+  int32_t n_good[8];  /* CheckRT's return value per candidate */
+  float parallax[8];
+  int32_t n_inliers;  /* inliers of the chosen model (N of ReconstructF / ReconstructH) */
+  int32_t reserved;
+} orbm_init_result; /* 112 B */
+
+typedef struct orbm_init_hyp {
+  int32_t idx[8]; /* mvSets[it]: positions in the gathered list */
+  float M[9];     /* H21i or F21i, row-major */
+  float score;    /* currentScore */
+} orbm_init_hyp; /* 72 B */
+
+typedef struct orbm_init_rt {
+  float R[9], t[3];
+} orbm_init_rt; /* 48 B */
+
+/* 8 x rand() per iteration, in order: the reference's stream (after srand(0),
+ * DUtils::Random::SeedRandOnce(0), for the first Initializer of a process).
+ * Host only. */
+int orbm_initializer_rand_fill(uint32_t* out, int iterations);
+/* The cap of max_iterations, the hypotheses per workgroup of the solve kernel
+ * and the largest pitch whose gathered list stays in LDS (0: the lists are
+ * always in the handle's workspace, no pitch takes another path). Each may be
+ * NULL. Host only. */
+int orbm_initializer_limits(int* max_iterations, int* chunk, int* lds_pitch);
+
+/* Host only: runs without a device, n1 / n2 not bounded by a handle. *status
+ * (may be NULL) gets 0 or bit 4096. acosf is the host libm's. */
+int orbm_initialize_host(const orbx_kp* kps1, int n1, const orbx_kp* kps2, int n2,
+                         const int* matches12, const orbm_camera* cam,
+                         const orbm_init_params* params, const uint32_t* rand8,
+                         orbm_init_result* result, float* R21, float* t21, float* Tcw, float* p3d,
+                         uint8_t* triangulated, int* matches12_out, uint8_t* inlier_h,
+                         uint8_t* inlier_f, float* T1, float* T2, float* H21, float* F21,
+                         orbm_init_hyp* hyp, orbm_init_rt* rt, int* status);
+
+/* The same on the device from host arrays, synchronous, one round trip. n1,
+ * n2 <= max_kps. Every output is that of the same arithmetic; only the
+ * parallax may differ from the host form's where the device's acosf rounds
+ * differently. Status bit 4096 is left for orbm_get_status. */
+int orbm_initialize(orbm_handle m, const orbx_kp* kps1, int n1, const orbx_kp* kps2, int n2,
+                    const int* matches12, const orbm_camera* cam, const orbm_init_params* params,
+                    const uint32_t* rand8, orbm_init_result* result, float* R21, float* t21,
+                    float* Tcw, float* p3d, uint8_t* triangulated, int* matches12_out,
+                    uint8_t* inlier_h, uint8_t* inlier_f, float* T1, float* T2, float* H21,
+                    float* F21, orbm_init_hyp* hyp, orbm_init_rt* rt);
+
+/* Device-resident and asynchronous on `stream`. Pair p's keypoints, matches12,
+ * triangulated, matches12_out, inlier_h and inlier_f at p*kp_pitch (d_n1[p] /
+ * d_n2[p] keypoints), p3d at 3*p*kp_pitch, its camera d_cam[p], its draws at
+ * d_rand8 + p*8*max_iterations, d_hyp + p*2*max_iterations, d_rt + 8*p,
+ * d_result[p], d_R21 + 9*p, d_t21 + 3*p, d_Tcw + 12*p, d_T1 / d_T2 / d_H21 /
+ * d_F21 + 9*p. params holds for every pair. Per-keypoint slots from d_n1[p] on
+ * are not touched; empty and too-small pairs are valid anywhere in the batch.
+ * kp_pitch <= max_kps. The output bits of a pair do not depend on the batch
+ * size, its slot, the run, the pitch or the split into chunks. */
+int orbm_initialize_batch(orbm_handle m, const orbx_kp* d_kps1, const int* d_n1,
+                          const orbx_kp* d_kps2, const int* d_n2, int kp_pitch,
+                          const int* d_matches12, const orbm_camera* d_cam,
+                          const orbm_init_params* params, const uint32_t* d_rand8, int pairs,
+                          orbm_init_result* d_result, float* d_R21, float* d_t21, float* d_Tcw,
+                          float* d_p3d, uint8_t* d_triangulated, int* d_matches12_out,
+                          uint8_t* d_inlier_h, uint8_t* d_inlier_f, float* d_T1, float* d_T2,
+                          float* d_H21, float* d_F21, orbm_init_hyp* d_hyp, orbm_init_rt* d_rt,
+                          void* stream);
 
 /* DBoW2::FeatureVector as CSR: nodes[k] ascending NodeIds; the feature
  * indices of node k are idx[off[k] .. off[k+1]). Each feature index appears

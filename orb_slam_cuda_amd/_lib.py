@@ -259,6 +259,15 @@ def lib() -> C.CDLL:
                                              [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 2 + [C.c_int] +
                                              [C.c_void_p] * 8)
         L.orbm_sim3_rand_fill.argtypes = [C.c_void_p, C.c_int]
+        # Initializer: kps1, n1, kps2, n2, matches12, cam, params, rand8, then the 15 outputs: result, R21, t21, Tcw,
+        # p3d, triangulated, matches12_out, inlier_h, inlier_f, T1, T2, H21, F21, hyp, rt
+        IZ = [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_void_p] * 15
+        L.orbm_initialize_host.argtypes = IZ + [C.POINTER(C.c_int)]
+        L.orbm_initialize.argtypes = [C.c_void_p] + IZ
+        L.orbm_initialize_batch.argtypes = ([C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 4 + [C.c_int] +
+                                            [C.c_void_p] * 16)
+        L.orbm_initializer_rand_fill.argtypes = [C.c_void_p, C.c_int]
+        L.orbm_initializer_limits.argtypes = [C.POINTER(C.c_int)] * 3
         L.orbm_sim3_limits.argtypes = [C.POINTER(C.c_int)] * 3
         L.orbm_sim3_iteration_table.argtypes = [C.c_double, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.orbm_prepare_sim3_match.argtypes = [C.POINTER(OrbmCamera), C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
@@ -427,6 +436,44 @@ def sim3_iteration_table(probability, min_inliers, max_iterations, n_max) -> np.
     out = np.zeros(n_max + 1, np.int32)
     check(lib().orbm_sim3_iteration_table(probability, min_inliers, max_iterations, n_max, ptr(out)), matcher=True)
     return out
+
+
+# orbm_init_params, orbm_init_result, orbm_init_hyp, orbm_init_rt (include/orbx_c.h): 16, 112, 72 and 48 bytes
+INIT_PARAMS_DTYPE = np.dtype([("sigma", "<f4"), ("max_iterations", "<i4"), ("min_parallax", "<f4"),
+                              ("min_triangulated", "<i4")])
+INIT_RESULT_DTYPE = np.dtype([("ok", "<i4"), ("code", "<i4"), ("n", "<i4"), ("model", "<i4"), ("SH", "<f4"),
+                              ("SF", "<f4"), ("RH", "<f4"), ("best_h", "<i4"), ("best_f", "<i4"), ("best_rt", "<i4"),
+                              ("n_good", "<i4", (8,)), ("parallax", "<f4", (8,)), ("n_inliers", "<i4"),
+                              ("reserved", "<i4")])
+INIT_HYP_DTYPE = np.dtype([("idx", "<i4", (8,)), ("M", "<f4", (9,)), ("score", "<f4")])
+INIT_RT_DTYPE = np.dtype([("R", "<f4", (9,)), ("t", "<f4", (3,))])
+assert (INIT_PARAMS_DTYPE.itemsize, INIT_RESULT_DTYPE.itemsize, INIT_HYP_DTYPE.itemsize,
+        INIT_RT_DTYPE.itemsize) == (16, 112, 72, 48)
+(INIT_TOO_FEW_MATCHES, INIT_NO_SCORE, INIT_DEGENERATE, INIT_NO_CLEAR_WINNER, INIT_TOO_FEW_POINTS, INIT_LOW_PARALLAX,
+ INIT_ACCEPTED) = range(1, 8)
+INIT_MODEL_H, INIT_MODEL_F = 1, 2
+STATUS_INIT_SKIPPED = 4096
+
+
+def init_params(sigma=1.0, max_iterations=200, min_parallax=1.0, min_triangulated=50) -> np.ndarray:
+    """One orbm_init_params record: Initializer(frame, sigma, iterations) and the 1.0, 50 Initialize passes on."""
+    p = np.zeros(1, INIT_PARAMS_DTYPE)
+    p[0] = (sigma, max_iterations, min_parallax, min_triangulated)
+    return p
+
+
+def initializer_rand_fill(iterations: int) -> np.ndarray:
+    """(iterations, 8) uint32: 8 x rand() per iteration from the C library's stream (orbm_initializer_rand_fill)."""
+    out = np.zeros((max(iterations, 0), 8), np.uint32)
+    check(lib().orbm_initializer_rand_fill(ptr(out), iterations), matcher=True)
+    return out
+
+
+def initializer_limits() -> tuple[int, int, int]:
+    """(cap of max_iterations, hypotheses per workgroup, LDS pitch limit: 0 = none)."""
+    a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
+    check(lib().orbm_initializer_limits(C.byref(a), C.byref(b), C.byref(c)), matcher=True)
+    return a.value, b.value, c.value
 
 
 # orbm_newpt_pair, orbm_new_point (include/orbx_c.h): 376 and 28 bytes

@@ -428,6 +428,36 @@ int sim3_ransac_host(const orbx_kp* kps1, int n1, const orbx_kp* kps2, int n2, c
                      const int* match12, const int* kp_index1, const float* level_sigma2, int nlevels,
                      const orbm_sim3_params* params, const uint32_t* rand3, orbm_sim3_result* result, float* s12,
                      float* R12, float* t12, orbm_pose* pose, uint8_t* inlier, orbm_sim3_hyp* hyp, int* status);
+// orbx_initializer.hip — Initializer: the two-view H / F RANSAC and reconstruction
+// of one frame pair per grid row (the arithmetic, the limits and status bit
+// 4096 are in orbx_initializer.cuh)
+struct InitzLaunchArgs {
+  const orbx_kp *kps1, *kps2;
+  const int *n1, *n2;
+  int kp_pitch;
+  const int* matches12;
+  const orbm_camera* cam;
+  orbm_init_params params;
+  const uint32_t* rand8;
+  int pairs;
+  orbm_init_result* result;  // every output or null
+  float *R21, *t21, *Tcw, *p3d;
+  uint8_t* triangulated;
+  int* matches12_out;
+  uint8_t *inlier_h, *inlier_f;
+  float *T1, *T2, *H21, *F21;
+  orbm_init_hyp* hyp;
+  orbm_init_rt* rt;
+  int* err;  // the handle's status word
+};
+// workspace of a launch: headers, gathered lists, hypotheses, flags and cosine keys
+size_t initializer_ws_bytes(int kp_pitch, int pairs, int max_iterations);
+int launch_initialize(const InitzLaunchArgs& P, void* ws, void* stream);
+int initialize_host(const orbx_kp* kps1, int n1, const orbx_kp* kps2, int n2, const int* matches12,
+                    const orbm_camera* cam, const orbm_init_params* params, const uint32_t* rand8,
+                    orbm_init_result* result, float* R21, float* t21, float* Tcw, float* p3d, uint8_t* triangulated,
+                    int* matches12_out, uint8_t* inlier_h, uint8_t* inlier_f, float* T1, float* T2, float* H21,
+                    float* F21, orbm_init_hyp* hyp, orbm_init_rt* rt, int* status);
 // orbx_triangulate.hip — SearchForTriangulation, one keyframe pair per workgroup
 struct TriSide {  // one side of the pairs; pitches of 0 share one keyframe across pairs
   const orbx_kp* kps;

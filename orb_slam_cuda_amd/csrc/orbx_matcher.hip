@@ -3,7 +3,8 @@
 // host-array entry points staged through the handle's arena. The kernels are in
 // orbx_top2.hip, orbx_bow.hip, orbx_init.hip, orbx_stereo.hip,
 // orbx_project.hip, orbx_project_pose.hip, orbx_frustum.hip,
-// orbx_triangulate.hip, orbx_mappoint.hip, orbx_poseopt.hip, orbx_sim3.hip and orbx_newpoints.hip.
+// orbx_triangulate.hip, orbx_mappoint.hip, orbx_poseopt.hip, orbx_sim3.hip, orbx_newpoints.hip and
+// orbx_initializer.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -17,6 +18,7 @@
 #include <vector>
 
 #include "orbx_hostutil.h"
+#include "orbx_initializer.cuh"
 #include "orbx_internal.h"
 #include "orbx_mappoint.cuh"
 #include "orbx_newpoints.cuh"
@@ -53,9 +55,10 @@ struct orbx_matcher {
   std::vector<int> sim3_tab_host;  // its source (the upload reads it)
   double sim3_prob = 0;
   int sim3_min_inliers = -1, sim3_max_iterations = -1;
+  DeviceBuf initz_ws;    // Initializer: headers, gathered lists, hypotheses, flags, cosine keys
   hipStream_t stream = nullptr;
-  WsOrder ws;  // stream order of cand / stereo_sad / pose_picks / view_ws / refresh_ws / po_ws / sim3_* / bow_* across caller streams
-  // streams of the launches that may set `err` (top-2, SearchByBoW, SearchLocalPoints, RefreshMapPoints, PoseOptimization, Sim3Solver)
+  WsOrder ws;  // stream order of cand / stereo_sad / pose_picks / view_ws / refresh_ws / po_ws / sim3_* / initz_ws / bow_* across caller streams
+  // streams of the launches that may set `err` (top-2, SearchByBoW, SearchLocalPoints, RefreshMapPoints, PoseOptimization, Sim3Solver, Initializer)
   StreamMarks errm;
   // staging for the synchronous entry points
   DeviceBuf stage;
@@ -215,7 +218,7 @@ int orbm_destroy(orbm_handle m) {
   m->errm.release();
   // the buffers go before the stream, not with the handle after it
   for (DeviceBuf* b : {&m->init_ws, &m->host_init_ws, &m->err, &m->stereo_sad, &m->bow_hist, &m->bow_rec, &m->pose_picks,
-                       &m->view_ws, &m->refresh_ws, &m->po_ws, &m->sim3_ws, &m->sim3_tab, &m->stage})
+                       &m->view_ws, &m->refresh_ws, &m->po_ws, &m->sim3_ws, &m->sim3_tab, &m->initz_ws, &m->stage})
     b->release();
   m->h_stage.release();
   if (m->stream) (void)hipStreamDestroy(m->stream);
@@ -1428,6 +1431,148 @@ int orbm_sim3_ransac(orbm_handle m, const orbx_kp* kps1, int n1, const orbx_kp* 
   if (s12) *s12 = srt[0];
   if (R12) std::memcpy(R12, srt + 1, 9 * sizeof(float));
   if (t12) std::memcpy(t12, srt + 10, 3 * sizeof(float));
+  return ORBX_OK;
+}
+
+// ---------------------------------------------------------------- Initializer
+namespace {
+int initz_check(const orbx_kp* kps1, int n1, const orbx_kp* kps2, int n2, const int* matches12, const orbm_camera* cam,
+                const orbm_init_params* P, const uint32_t* rand8) {
+  if (n1 < 0 || n2 < 0 || !cam || !P || !rand8 || (n1 && (!kps1 || !matches12)) || (n2 && !kps2))
+    return g_merr.fail(ORBX_EINVAL, "bad argument");
+  if (P->max_iterations < 1 || P->max_iterations > kInitzMaxIts)
+    return g_merr.fail(ORBX_ECAPACITY, "max_iterations %d outside 1..%d", P->max_iterations, kInitzMaxIts);
+  return ORBX_OK;
+}
+}  // namespace
+
+int orbm_initialize_host(const orbx_kp* kps1, int n1, const orbx_kp* kps2, int n2, const int* matches12,
+                         const orbm_camera* cam, const orbm_init_params* params, const uint32_t* rand8,
+                         orbm_init_result* result, float* R21, float* t21, float* Tcw, float* p3d,
+                         uint8_t* triangulated, int* matches12_out, uint8_t* inlier_h, uint8_t* inlier_f, float* T1,
+                         float* T2, float* H21, float* F21, orbm_init_hyp* hyp, orbm_init_rt* rt, int* status) {
+  int rc;
+  if ((rc = initz_check(kps1, n1, kps2, n2, matches12, cam, params, rand8))) return rc;
+  return initialize_host(kps1, n1, kps2, n2, matches12, cam, params, rand8, result, R21, t21, Tcw, p3d, triangulated,
+                         matches12_out, inlier_h, inlier_f, T1, T2, H21, F21, hyp, rt, status);
+}
+
+int orbm_initialize_batch(orbm_handle m, const orbx_kp* d_kps1, const int* d_n1, const orbx_kp* d_kps2,
+                          const int* d_n2, int kp_pitch, const int* d_matches12, const orbm_camera* d_cam,
+                          const orbm_init_params* params, const uint32_t* d_rand8, int pairs,
+                          orbm_init_result* d_result, float* d_R21, float* d_t21, float* d_Tcw, float* d_p3d,
+                          uint8_t* d_triangulated, int* d_matches12_out, uint8_t* d_inlier_h, uint8_t* d_inlier_f,
+                          float* d_T1, float* d_T2, float* d_H21, float* d_F21, orbm_init_hyp* d_hyp,
+                          orbm_init_rt* d_rt, void* stream) {
+  if (!m || !d_kps1 || !d_n1 || !d_kps2 || !d_n2 || !d_matches12 || !d_cam || !params || !d_rand8 || pairs < 1 ||
+      kp_pitch < 1)
+    return g_merr.fail(ORBX_EINVAL, "bad argument");
+  if (params->max_iterations < 1 || params->max_iterations > kInitzMaxIts)
+    return g_merr.fail(ORBX_ECAPACITY, "max_iterations %d outside 1..%d", params->max_iterations, kInitzMaxIts);
+  if (kp_pitch > m->max_kps)
+    return g_merr.fail(ORBX_ECAPACITY, "kp_pitch %d above the handle's max_kps %d", kp_pitch, m->max_kps);
+  if (pairs > 65535) return g_merr.fail(ORBX_ECAPACITY, "%d pairs above 65535", pairs);
+  HIP_OK(g_merr, hipSetDevice(m->device));
+  hipStream_t s = (hipStream_t)stream;
+  const size_t need = initializer_ws_bytes(kp_pitch, pairs, params->max_iterations);
+  // the workspace is the handle's: after its last user, whatever its stream
+  if (m->ws.before(s)) return g_merr.fail(ORBX_EDEVICE, "stream wait on the workspace failed");
+  if (m->initz_ws.n < need) {
+    // replaced memory must not be in use: wait for the last user
+    if (m->ws.ev) HIP_OK(g_merr, hipEventSynchronize(m->ws.ev));
+    if (m->initz_ws.reserve(need) != hipSuccess) return g_merr.fail(ORBX_ENOMEM, "Initializer workspace");
+  }
+  InitzLaunchArgs A{};
+  A.kps1 = d_kps1;
+  A.kps2 = d_kps2;
+  A.n1 = d_n1;
+  A.n2 = d_n2;
+  A.kp_pitch = kp_pitch;
+  A.matches12 = d_matches12;
+  A.cam = d_cam;
+  A.params = *params;
+  A.rand8 = d_rand8;
+  A.pairs = pairs;
+  A.result = d_result;
+  A.R21 = d_R21;
+  A.t21 = d_t21;
+  A.Tcw = d_Tcw;
+  A.p3d = d_p3d;
+  A.triangulated = d_triangulated;
+  A.matches12_out = d_matches12_out;
+  A.inlier_h = d_inlier_h;
+  A.inlier_f = d_inlier_f;
+  A.T1 = d_T1;
+  A.T2 = d_T2;
+  A.H21 = d_H21;
+  A.F21 = d_F21;
+  A.hyp = d_hyp;
+  A.rt = d_rt;
+  A.err = m->err.as<int>();
+  if (launch_initialize(A, m->initz_ws.p, stream))
+    return g_merr.fail(ORBX_EDEVICE, "Initializer launch: %s", hipGetErrorString(hipGetLastError()));
+  if (m->ws.after(s) || m->errm.mark(s)) return g_merr.fail(ORBX_EDEVICE, "event record failed");
+  return ORBX_OK;
+}
+
+int orbm_initialize(orbm_handle m, const orbx_kp* kps1, int n1, const orbx_kp* kps2, int n2, const int* matches12,
+                    const orbm_camera* cam, const orbm_init_params* params, const uint32_t* rand8,
+                    orbm_init_result* result, float* R21, float* t21, float* Tcw, float* p3d, uint8_t* triangulated,
+                    int* matches12_out, uint8_t* inlier_h, uint8_t* inlier_f, float* T1, float* T2, float* H21,
+                    float* F21, orbm_init_hyp* hyp, orbm_init_rt* rt) {
+  int rc;
+  if (!m) return g_merr.fail(ORBX_EINVAL, "bad argument");
+  if ((rc = initz_check(kps1, n1, kps2, n2, matches12, cam, params, rand8))) return rc;
+  if (std::max(n1, n2) > m->max_kps)
+    return g_merr.fail(ORBX_ECAPACITY, "%d keypoints above the handle's max_kps %d", std::max(n1, n2), m->max_kps);
+  HIP_OK(g_merr, hipSetDevice(m->device));
+  const size_t kp = std::max(std::max(n1, n2), 1), its = params->max_iterations;
+  Stage st(m);
+  auto dk1 = st.slot<orbx_kp>(kp);
+  auto dk2 = st.slot<orbx_kp>(kp);
+  auto dn = st.slot<int>(2);
+  auto d12 = st.slot<int>(kp);
+  auto dc = st.slot<orbm_camera>(1);
+  auto drand = st.slot<uint32_t>(8 * its);
+  auto dres = st.slot<orbm_init_result>(1);
+  auto dmat = st.slot<float>(60);  // R21 9, t21 3, Tcw 12, T1 9, T2 9, H21 9, F21 9
+  auto dp3 = st.slot<float>(3 * kp);
+  auto dtri = st.slot<uint8_t>(kp);
+  auto dout = st.slot<int>(kp);
+  auto dih = st.slot<uint8_t>(kp);
+  auto dif = st.slot<uint8_t>(kp);
+  auto dhyp = st.slot<orbm_init_hyp>(2 * its);
+  auto drt = st.slot<orbm_init_rt>(8);
+  const int counts[2] = {n1, n2};
+  // the outputs go up too: what the call leaves untouched comes back as it was
+  float mat[60] = {};
+  float* const mp[7] = {R21, t21, Tcw, T1, T2, H21, F21};
+  const int mo[8] = {0, 9, 12, 24, 33, 42, 51, 60};
+  for (int k = 0; k < 7; ++k)
+    if (mp[k]) std::memcpy(mat + mo[k], mp[k], (mo[k + 1] - mo[k]) * sizeof(float));
+  float* dm = dmat;
+  if ((rc = st.reserve())) return rc;
+  dm = dmat;
+  if ((rc = st.up(dk1, kps1, n1)) || (rc = st.up(dk2, kps2, n2)) || (rc = st.up(dn, counts, 2)) ||
+      (rc = st.up(d12, matches12, n1)) || (rc = st.up(dc, cam, 1)) || (rc = st.up(drand, rand8, 8 * its)) ||
+      (rc = st.up(dres, (const orbm_init_result*)result, 1)) || (rc = st.up(dmat, (const float*)mat, 60)) ||
+      (rc = st.up(dp3, (const float*)p3d, 3 * (size_t)n1)) || (rc = st.up(dtri, (const uint8_t*)triangulated, n1)) ||
+      (rc = st.up(dout, (const int*)matches12_out, n1)) || (rc = st.up(dih, (const uint8_t*)inlier_h, n1)) ||
+      (rc = st.up(dif, (const uint8_t*)inlier_f, n1)) || (rc = st.up(dhyp, (const orbm_init_hyp*)hyp, 2 * its)) ||
+      (rc = st.up(drt, (const orbm_init_rt*)rt, 8)) ||
+      (rc = orbm_initialize_batch(m, dk1, dn, dk2, (int*)dn + 1, (int)kp, d12, dc, params, drand, 1, dres, dm, dm + 9,
+                                  dm + 12, p3d ? (float*)dp3 : nullptr, triangulated ? (uint8_t*)dtri : nullptr,
+                                  matches12_out ? (int*)dout : nullptr, inlier_h ? (uint8_t*)dih : nullptr,
+                                  inlier_f ? (uint8_t*)dif : nullptr, dm + 24, dm + 33, dm + 42, dm + 51,
+                                  hyp ? (orbm_init_hyp*)dhyp : nullptr, rt ? (orbm_init_rt*)drt : nullptr, st.st)) ||
+      (rc = st.down(mat, dmat, 60)) || (result && (rc = st.down(result, dres, 1))) ||
+      (p3d && (rc = st.down(p3d, dp3, 3 * (size_t)n1))) || (triangulated && (rc = st.down(triangulated, dtri, n1))) ||
+      (matches12_out && (rc = st.down(matches12_out, dout, n1))) || (inlier_h && (rc = st.down(inlier_h, dih, n1))) ||
+      (inlier_f && (rc = st.down(inlier_f, dif, n1))) || (hyp && (rc = st.down(hyp, dhyp, 2 * its))) ||
+      (rt && (rc = st.down(rt, drt, 8))) || (rc = st.finish()))
+    return rc;
+  for (int k = 0; k < 7; ++k)
+    if (mp[k]) std::memcpy(mp[k], mat + mo[k], (mo[k + 1] - mo[k]) * sizeof(float));
   return ORBX_OK;
 }
 

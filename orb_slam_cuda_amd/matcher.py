@@ -32,6 +32,10 @@ for Sim3Solver (src/Sim3Solver.cc), loop closing's RANSAC between SearchByBoW an
 
     (s12, R12, t12), inlier, result = m.Sim3Ransac(kps1, mps1, cam1, kps2, mps2, cam2, match12, sigma2, rand3)
 
+for Initializer (src/Initializer.cc), the monocular bootstrap after SearchForInitialization:
+
+    ok, R21, t21, vP3D, vbTriangulated = m.Initialize(kps1, kps2, vnMatches12, cam)
+
 and for the Frame constructors' tail (src/Frame.cc:118-227, 403-463, 642-663):
 
     F = ExtractRGBD(extractor, imGray, imDepth, K, distCoef, mbf, DepthMapFactor)  # one device round trip
@@ -921,6 +925,60 @@ class ORBmatcher:
             return None, inlier[:n1], r
         self.last_sim3_poses = poses
         return (srt[0], srt[1:10].reshape(3, 3).copy(), srt[10:13].copy()), inlier[:n1], r
+
+    def Initialize(self, kps1, kps2, matches12, cam, rand8=None, *, sigma=1.0, max_iterations=200, min_parallax=1.0,
+                   min_triangulated=50, want_hyp=False, host=False):
+        """Initializer::Initialize (src/Initializer.cc:44-121) with everything under it, in one device round trip
+        (orbm_initialize), or on the host alone with host=True (orbm_initialize_host). kps1 / kps2: KP_DTYPE
+        (mvKeysUn of the reference and the current frame); matches12: int32 per keypoint of frame 1, what
+        SearchForInitialization wrote into vnMatches12; cam: _lib.camera(...) (fx, fy, cx, cy are read); rand8:
+        (max_iterations, 8) uint32 raw rand() values (default: _lib.initializer_rand_fill, the C library's stream).
+        Returns (ok, R21 (3, 3), t21 (3,), vP3D (n1, 3), vbTriangulated (n1,) uint8); R21 and t21 are None unless
+        ok. Everything else stays in self.last_init: a dict with result (INIT_RESULT_DTYPE record), Tcw (3, 4),
+        matches12 (the input with untriangulated entries set to -1, src/Tracking.cc:688-693), inlier_h / inlier_f
+        (per gathered match), T1, T2, H21, F21, rt (INIT_RT_DTYPE x 8) and, with want_hyp, hyp (INIT_HYP_DTYPE x
+        2*max_iterations: homographies, then fundamental matrices). A matches12 value >= len(kps2) is left out
+        and sets bit 4096 of status() (host=True: self.last_host_status)."""
+        kps1 = np.ascontiguousarray(kps1, KP_DTYPE)
+        kps2 = np.ascontiguousarray(kps2, KP_DTYPE)
+        n1, n2 = len(kps1), len(kps2)
+        m12 = np.ascontiguousarray(matches12, np.int32)
+        if len(m12) != n1:
+            raise _lib.OrbxError(_lib.ORBX_EINVAL, "one matches12 entry per keypoint of frame 1")
+        if rand8 is None:
+            rand8 = _lib.initializer_rand_fill(max_iterations)
+        rand8 = np.ascontiguousarray(rand8, np.uint32)
+        if rand8.size < 8 * max_iterations:
+            raise _lib.OrbxError(_lib.ORBX_EINVAL, "rand8 needs 8 values per iteration")
+        par = _lib.init_params(sigma, max_iterations, min_parallax, min_triangulated)
+        nn = max(n1, 1)
+        res = np.zeros(1, _lib.INIT_RESULT_DTYPE)
+        mats = np.zeros(60, np.float32)  # R21 9, t21 3, Tcw 12, T1 9, T2 9, H21 9, F21 9
+        p3d = np.zeros((nn, 3), np.float32)
+        tri = np.zeros(nn, np.uint8)
+        m12o = np.full(nn, -1, np.int32)
+        inl_h = np.zeros(nn, np.uint8)
+        inl_f = np.zeros(nn, np.uint8)
+        hyp = np.zeros(2 * max_iterations, _lib.INIT_HYP_DTYPE) if want_hyp else None
+        rt = np.zeros(8, _lib.INIT_RT_DTYPE)
+        args = (ptr(kps1), n1, ptr(kps2), n2, ptr(m12), C.addressof(cam), ptr(par), ptr(rand8), ptr(res),
+                ptr(mats[0:9]), ptr(mats[9:12]), ptr(mats[12:24]), ptr(p3d), ptr(tri), ptr(m12o), ptr(inl_h),
+                ptr(inl_f), ptr(mats[24:33]), ptr(mats[33:42]), ptr(mats[42:51]), ptr(mats[51:60]), ptr(hyp), ptr(rt))
+        if host:
+            st = C.c_int(0)
+            check(lib().orbm_initialize_host(*args, C.byref(st)), matcher=True)
+            self.last_host_status = st.value
+        else:
+            check(lib().orbm_initialize(self._h, *args), matcher=True)
+        r = res[0]
+        N = int(r["n"])
+        self.last_init = dict(result=r, Tcw=mats[12:24].reshape(3, 4).copy(), matches12=m12o[:n1],
+                              inlier_h=inl_h[:N], inlier_f=inl_f[:N], T1=mats[24:33].reshape(3, 3).copy(),
+                              T2=mats[33:42].reshape(3, 3).copy(), H21=mats[42:51].reshape(3, 3).copy(),
+                              F21=mats[51:60].reshape(3, 3).copy(), rt=rt, hyp=hyp)
+        if not r["ok"]:
+            return False, None, None, p3d[:n1], tri[:n1]
+        return True, mats[0:9].reshape(3, 3).copy(), mats[9:12].copy(), p3d[:n1], tri[:n1]
 
     def CreateNewMapPoints(self, pKF1: KeyFrame, neighbours, matches12=None, *, host=False):
         """LocalMapping::CreateNewMapPoints' loop (src/LocalMapping.cc:270-484) for the current keyframe pKF1

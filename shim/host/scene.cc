@@ -16,6 +16,7 @@
 //   op 11 Optimizer::PoseOptimization(&CurrentFrame)       Tracking.cc:975, 1020
 //   op 12 Sim3Solver(pKF1, pKF2, vpMatches12, fix), SetRansacParameters, iterate(k)...  LoopClosing.cc:313-340
 //   op 13 CreateNewMapPoints(pKF, vpNeighKFs, bMonocular): the search, triangulation and refresh of LocalMapping.cc:270-483
+//   op 14 Initializer(ReferenceFrame, sigma, iterations), Initialize(CurrentFrame, vMatches12, ...)  Tracking.cc:638-700
 // --scene-latency: the same scene rebuilt per call, only the method call on
 // the host clock (median / p99 over the calls after the warm ones).
 // Scene file: records of [u32 name length][name][u32 dtype 0 u8 / 1 i32 /
@@ -35,6 +36,7 @@
 #include <vector>
 
 #include "Frame.h"
+#include "Initializer.h"
 #include "KeyFrame.h"
 #include "LocalMapping.h"
 #include "MapPoint.h"
@@ -546,6 +548,46 @@ static void run_op(const Scene& s, std::vector<int>& res, double* ms) {
           int w;
           memcpy(&w, q.descriptor.data + 4 * k, 4);
           res.push_back(w);
+        }
+      }
+      break;
+    }
+    case 14: {  // -> [returned, the result's code, model, n, then with a true return the bits of R21 (9), t21 (3),
+                // vbTriangulated per keypoint of frame 1 and the bits of vP3D (3 per keypoint)]
+      auto F1 = frame(s, "A", pool);
+      auto F2 = frame(s, "B", pool);
+      const auto cam = s.vec<float>("A_cam");
+      F1->mK = cv::Mat(3, 3, CV_32F);
+      for (int k = 0; k < 9; ++k) F1->mK.at<float>(k / 3, k % 3) = k % 4 == 0 ? 1.f : 0.f;
+      F1->mK.at<float>(0, 0) = cam[0];
+      F1->mK.at<float>(1, 1) = cam[1];
+      F1->mK.at<float>(0, 2) = cam[2];
+      F1->mK.at<float>(1, 2) = cam[3];
+      const std::vector<int> m12 = s.vec<int>("matches12");
+      auto bits = [](float v) {
+        int b;
+        memcpy(&b, &v, 4);
+        return b;
+      };
+      tic();
+      Initializer init(*F1, s.f("sigma"), s.i("max_iterations"));
+      cv::Mat R21, t21;
+      std::vector<cv::Point3f> vP3D;
+      std::vector<bool> vbTriangulated;
+      const bool ok = init.Initialize(*F2, m12, R21, t21, vP3D, vbTriangulated);
+      toc();
+      res.push_back(ok ? 1 : 0);
+      res.push_back(init.LastResult().code);
+      res.push_back(init.LastResult().model);
+      res.push_back(init.LastResult().n);
+      if (ok) {
+        for (int k = 0; k < 9; ++k) res.push_back(bits(R21.at<float>(k / 3, k % 3)));
+        for (int k = 0; k < 3; ++k) res.push_back(bits(t21.at<float>(k)));
+        for (bool b : vbTriangulated) res.push_back(b ? 1 : 0);
+        for (const cv::Point3f& q : vP3D) {
+          res.push_back(bits(q.x));
+          res.push_back(bits(q.y));
+          res.push_back(bits(q.z));
         }
       }
       break;
