@@ -85,6 +85,8 @@
  *                          include/Optimizer.h:53, src/Optimizer.cc:334-543
  *   orbm_sim3_ransac / _batch / _host  Sim3Solver (ctor, SetRansacParameters,
  *                          iterate / find)  include/Sim3Solver.h, src/Sim3Solver.cc:37-423
+ *   orbm_optimize_sim3 / _batch / _host  Optimizer::OptimizeSim3  include/Optimizer.h:57,
+ *                          src/Optimizer.cc:1190-1385 (LoopClosing::ComputeSim3)
  *   orbm_create_new_map_points / _batch / _host  the loop over vMatchedIndices of
  *                          LocalMapping::CreateNewMapPoints  src/LocalMapping.cc:317-464
  *   orbm_compute_f12       LocalMapping::ComputeF12  src/LocalMapping.cc:572-589
@@ -325,7 +327,10 @@ int orbm_destroy(orbm_handle m);
  * has mvDepth <= 0 where UnprojectStereo needs it; bit 2048: the same calls
  * found more new points than `capacity` and dropped the excess; bit 4096:
  * orbm_initialize_batch / orbm_initialize left a match out whose matches12
- * value is at or above n2).
+ * value is at or above n2; bit 8192: orbm_optimize_sim3_batch /
+ * orbm_optimize_sim3 left an entry out whose match12, found12 or found21
+ * value is at or above the other keyframe's count or whose keypoint's octave
+ * is outside [0, nlevels)).
  * SearchForInitialization keeps no
  * candidate lists (8 smallest keys per query) and never sets it. Waits for
  * the matcher's own launches that may set it (on whatever streams they ran),
@@ -949,6 +954,103 @@ int orbm_sim3_ransac_batch(orbm_handle m, const orbx_kp* d_kps1, const int* d_n1
                            int pairs, orbm_sim3_result* d_result, float* d_s12, float* d_R12,
                            float* d_t12, orbm_pose* d_pose, uint8_t* d_inlier, orbm_sim3_hyp* d_hyp,
                            void* stream);
+
+/* ------------------------------------------------- Optimizer::OptimizeSim3
+ * The refinement of a loop candidate's Sim3 (src/Optimizer.cc:1190-1385,
+ * called at src/LoopClosing.cc:365) between SearchBySim3 and
+ * SearchByProjection(pKF, Scw, ...): one 7-DoF vertex, the two reprojection
+ * edges x1 = S12*X2 and x2 = S21*X1 per match with Huber kernels, optimize(5),
+ * the removal of pairs with a chi2 above th2, optimize(5 or 10) and a second
+ * check. The arithmetic restates what the reference makes g2o do, in double,
+ * with g2o's numeric Jacobian.
+ *
+ * Inputs per keyframe pair, as orbm_sim3_ransac takes them: kps1 / kps2 =
+ * mvKeysUn (x, y, octave are read), mps1 / mps2 = one orbm_map_point_world per
+ * keypoint (pos and valid are read), cam1 / cam2 with Tcw = T1w / T2w,
+ * inv_sigma2 = mvInvLevelSigma2 (nlevels <= 16 floats, host), *s12, R12[9]
+ * (row-major), t12[3] = the RANSAC's estimate, th2 (the reference passes 10),
+ * fix_scale = mbFixScale.
+ * vpMatches1 is built from match12 (the BoW matches), inlier (uint8 per i1, the
+ * RANSAC's; NULL keeps every match) and found12 / found21 (both or neither:
+ * the two ORBM_PROJ_SIM3_MATCH outputs, per point of KF1 the keypoint of KF2
+ * it matched and the reverse): m[i1] = match12[i1] where that is >= 0 and the
+ * inlier flag is set (src/LoopClosing.cc:352-357); otherwise found12[i1] when
+ * i2 = found12[i1] is in [0, n2), is not the target of a kept match and
+ * found21[i2] == i1 (src/ORBmatcher.cc:1295-1312); otherwise -1. Entry i1
+ * gets an edge pair when m[i1] >= 0, mps1[i1].valid and mps2[m[i1]].valid, in
+ * i1 order. A match12, found12 or found21 value at or above the other
+ * keyframe's count makes m[i1] = -1, an octave outside [0, nlevels) leaves the
+ * pair out; both set status bit 8192.
+ *
+ * Outputs (each may be NULL): match12_out[i1] = vpMatches1 as the function
+ * leaves it: m[i1], or -1 where the first or the second check rejected the
+ * pair (must not overlap the inputs); S12[8] = g2oS12 on return as (qx, qy,
+ * qz, qw, tx, ty, tz, s), the input through Quaterniond(Matrix3d) when the
+ * function returns 0 before the second optimisation; Scw[12] = rows 0..2 of
+ * Converter::toCvMat(gScm * gSmw), gSmw = Sim3(R2w, t2w, 1.0)
+ * (src/LoopClosing.cc:372-374); pose = orbm_prepare_pose(ORBM_PROJ_SIM3, cam1
+ * with Tcw = Scw), byte for byte; *result below; lin[36] = the upper triangle
+ * of H row by row (28), b (7) and the robust chi2 of the first linearisation
+ * of the first optimize, zeros without an edge pair (a diagnostic). */
+typedef struct orbm_optsim3_result {
+  int32_t ret;             /* the function's return value: nIn, or 0 */
+  int32_t n_corr;          /* nCorrespondences */
+  int32_t n_bad;           /* nBad of the first check */
+  int32_t rounds;          /* optimisations run: 1 or 2 */
+  int32_t more_iterations; /* nMoreIterations: 10 when n_bad > 0, else 5 */
+  int32_t trials;          /* Levenberg-Marquardt trials of both rounds */
+  int32_t rejected;        /* trials whose step was rejected */
+  int32_t reserved;
+} orbm_optsim3_result; /* 32 B */
+
+/* Host only: runs without a device, n1 / n2 not bounded by a handle. Edges
+ * accumulate in i1 order, e12 before e21, as g2o's do. *status (may be NULL)
+ * gets 0 or bit 8192. */
+int orbm_optimize_sim3_host(const orbx_kp* kps1, int n1, const orbx_kp* kps2, int n2,
+                            const orbm_map_point_world* mps1, const orbm_map_point_world* mps2,
+                            const orbm_camera* cam1, const orbm_camera* cam2, const int* match12,
+                            const uint8_t* inlier, const int* found12, const int* found21,
+                            const float* inv_sigma2, int nlevels, const float* s12, const float* R12,
+                            const float* t12, float th2, int fix_scale, int* match12_out, double* S12,
+                            float* Scw, orbm_pose* pose, orbm_optsim3_result* result, double* lin,
+                            int* status);
+
+/* The same on the device from host arrays, synchronous, one round trip.
+ * n1, n2 <= max_kps. Sums over the edges are reduced lane -> wave -> workgroup
+ * in a fixed order and exp / sin / cos are the device's, so S12 differs from
+ * the host form's as it does between two edge orders on the host (the 1e-9
+ * difference quotient amplifies a last-place change of a sum; DESIGN.md gives
+ * the measured spread); flags and counts are those of the same arithmetic.
+ * Status bit 8192 is left for orbm_get_status. */
+int orbm_optimize_sim3(orbm_handle m, const orbx_kp* kps1, int n1, const orbx_kp* kps2, int n2,
+                       const orbm_map_point_world* mps1, const orbm_map_point_world* mps2,
+                       const orbm_camera* cam1, const orbm_camera* cam2, const int* match12,
+                       const uint8_t* inlier, const int* found12, const int* found21,
+                       const float* inv_sigma2, int nlevels, const float* s12, const float* R12,
+                       const float* t12, float th2, int fix_scale, int* match12_out, double* S12,
+                       float* Scw, orbm_pose* pose, orbm_optsim3_result* result, double* lin);
+
+/* Device-resident and asynchronous on `stream`, one workgroup per pair. The
+ * pitches and per-pair counts are orbm_sim3_ransac_batch's, so that call's
+ * buffers pass straight through: pair p's keypoints, match12, inlier, found12,
+ * found21 and match12_out at p*kp_pitch (d_n1[p] / d_n2[p] of them), its map
+ * points at p*mp_pitch (mp_pitch >= kp_pitch), d_cam1[p] / d_cam2[p], d_s12[p],
+ * d_R12 + 9*p, d_t12 + 3*p; d_S12 + 8*p, d_Scw + 12*p, d_pose[p], d_result[p],
+ * d_lin + 36*p. th2 and fix_scale hold for every pair. match12_out slots from
+ * d_n1[p] on are not touched; empty pairs are valid anywhere in the batch.
+ * kp_pitch <= max_kps; the edge pairs stay in LDS up to a pitch of 1024, above
+ * that in the handle's workspace. The output bits of a pair do not depend on
+ * the batch size, its slot, the run or the pitch. */
+int orbm_optimize_sim3_batch(orbm_handle m, const orbx_kp* d_kps1, const int* d_n1,
+                             const orbx_kp* d_kps2, const int* d_n2, int kp_pitch,
+                             const orbm_map_point_world* d_mps1, const orbm_map_point_world* d_mps2,
+                             int mp_pitch, const orbm_camera* d_cam1, const orbm_camera* d_cam2,
+                             const int* d_match12, const uint8_t* d_inlier, const int* d_found12,
+                             const int* d_found21, const float* inv_sigma2, int nlevels,
+                             const float* d_s12, const float* d_R12, const float* d_t12, float th2,
+                             int fix_scale, int pairs, int* d_match12_out, double* d_S12, float* d_Scw,
+                             orbm_pose* d_pose, orbm_optsim3_result* d_result, double* d_lin,
+                             void* stream);
 
 /* ------------------------------------------------------------ Initializer
  * The monocular bootstrap between SearchForInitialization and

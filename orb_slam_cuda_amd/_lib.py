@@ -259,6 +259,15 @@ def lib() -> C.CDLL:
                                              [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 2 + [C.c_int] +
                                              [C.c_void_p] * 8)
         L.orbm_sim3_rand_fill.argtypes = [C.c_void_p, C.c_int]
+        # kps1, n1, kps2, n2, mps1, mps2, cam1, cam2, match12, inlier, found12, found21, inv_sigma2, nlevels, s12,
+        # R12, t12, th2, fix_scale, match12_out, S12, Scw, pose, result, lin
+        O3 = ([C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 9 + [C.c_int] + [C.c_void_p] * 3 +
+              [C.c_float, C.c_int] + [C.c_void_p] * 6)
+        L.orbm_optimize_sim3_host.argtypes = O3 + [C.POINTER(C.c_int)]
+        L.orbm_optimize_sim3.argtypes = [C.c_void_p] + O3
+        L.orbm_optimize_sim3_batch.argtypes = ([C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 2 + [C.c_int] +
+                                               [C.c_void_p] * 7 + [C.c_int] + [C.c_void_p] * 3 +
+                                               [C.c_float, C.c_int, C.c_int] + [C.c_void_p] * 7)
         # Initializer: kps1, n1, kps2, n2, matches12, cam, params, rand8, then the 15 outputs: result, R21, t21, Tcw,
         # p3d, triangulated, matches12_out, inlier_h, inlier_f, T1, T2, H21, F21, hyp, rt
         IZ = [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_void_p] * 15
@@ -407,6 +416,13 @@ POSE_DTYPE = np.dtype([("Rt", "<f4", (12,)), ("Ow", "<f4", (3,)), ("fx", "<f4"),
                        ("cy", "<f4"), ("mbf", "<f4"), ("level_mode", "<i4"), ("Rt2", "<f4", (12,))])  # orbm_pose
 assert CAMERA_DTYPE.itemsize == 72 and POSE_DTYPE.itemsize == 132
 STATUS_SIM3_SKIPPED = 512
+# orbm_optsim3_result (include/orbx_c.h): 32 bytes
+OPTSIM3_RESULT_DTYPE = np.dtype([("ret", "<i4"), ("n_corr", "<i4"), ("n_bad", "<i4"), ("rounds", "<i4"),
+                                 ("more_iterations", "<i4"), ("trials", "<i4"), ("rejected", "<i4"),
+                                 ("reserved", "<i4")])
+assert OPTSIM3_RESULT_DTYPE.itemsize == 32
+STATUS_OPTSIM3_SKIPPED = 8192
+OPTSIM3_LDS_PITCH = 1024  # pair pitches up to this keep the edge pairs in LDS
 
 
 def sim3_params(probability=0.99, min_inliers=20, max_iterations=300, fix_scale=False, first_iteration=0,

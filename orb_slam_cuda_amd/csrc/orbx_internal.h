@@ -428,6 +428,33 @@ int sim3_ransac_host(const orbx_kp* kps1, int n1, const orbx_kp* kps2, int n2, c
                      const int* match12, const int* kp_index1, const float* level_sigma2, int nlevels,
                      const orbm_sim3_params* params, const uint32_t* rand3, orbm_sim3_result* result, float* s12,
                      float* R12, float* t12, orbm_pose* pose, uint8_t* inlier, orbm_sim3_hyp* hyp, int* status);
+// orbx_optsim3.hip — Optimizer::OptimizeSim3, one keyframe pair per workgroup
+// (the arithmetic, the LDS limit and status bit 8192 are in orbx_optsim3.cuh)
+struct OptSim3Args {
+  const orbx_kp *kps1, *kps2;
+  const int *n1, *n2;
+  int kp_pitch, mp_pitch;
+  const orbm_map_point_world *mps1, *mps2;
+  const orbm_camera *cam1, *cam2;
+  const int* match12;
+  const uint8_t* inlier;           // or null
+  const int *found12, *found21;    // both or null
+  const float* inv_sigma2;         // host, nlevels
+  int nlevels;
+  const float *s12, *R12, *t12;
+  float th2;
+  int fix_scale, pairs;
+  int* match12_out;             // every output or null
+  double* S12;
+  float* Scw;
+  orbm_pose* pose;
+  orbm_optsim3_result* result;
+  double* lin;
+  int* err;  // the handle's status word
+};
+size_t optsim3_ws_bytes(int kp_pitch, int pairs);  // workspace of a launch (0 up to kOs3LdsCorr)
+int launch_optimize_sim3(const OptSim3Args& P, void* ws, void* stream);
+int optimize_sim3_host(const OptSim3Args& P, int n1, int n2, int* status);  // pair 0 of host arrays
 // orbx_initializer.hip — Initializer: the two-view H / F RANSAC and reconstruction
 // of one frame pair per grid row (the arithmetic, the limits and status bit
 // 4096 are in orbx_initializer.cuh)

@@ -3,8 +3,8 @@
 // host-array entry points staged through the handle's arena. The kernels are in
 // orbx_top2.hip, orbx_bow.hip, orbx_init.hip, orbx_stereo.hip,
 // orbx_project.hip, orbx_project_pose.hip, orbx_frustum.hip,
-// orbx_triangulate.hip, orbx_mappoint.hip, orbx_poseopt.hip, orbx_sim3.hip, orbx_newpoints.hip and
-// orbx_initializer.hip.
+// orbx_triangulate.hip, orbx_mappoint.hip, orbx_poseopt.hip, orbx_sim3.hip, orbx_optsim3.hip,
+// orbx_newpoints.hip and orbx_initializer.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -22,6 +22,7 @@
 #include "orbx_internal.h"
 #include "orbx_mappoint.cuh"
 #include "orbx_newpoints.cuh"
+#include "orbx_optsim3.cuh"
 #include "orbx_posemath.cuh"
 #include "orbx_poseopt.cuh"
 #include "orbx_sim3.cuh"
@@ -56,9 +57,10 @@ struct orbx_matcher {
   double sim3_prob = 0;
   int sim3_min_inliers = -1, sim3_max_iterations = -1;
   DeviceBuf initz_ws;    // Initializer: headers, gathered lists, hypotheses, flags, cosine keys
+  DeviceBuf os3_ws;      // OptimizeSim3: edge pair records and bitmaps of pair pitches above kOs3LdsCorr
   hipStream_t stream = nullptr;
-  WsOrder ws;  // stream order of cand / stereo_sad / pose_picks / view_ws / refresh_ws / po_ws / sim3_* / initz_ws / bow_* across caller streams
-  // streams of the launches that may set `err` (top-2, SearchByBoW, SearchLocalPoints, RefreshMapPoints, PoseOptimization, Sim3Solver, Initializer)
+  WsOrder ws;  // stream order of cand / stereo_sad / pose_picks / view_ws / refresh_ws / po_ws / sim3_* / initz_ws / os3_ws / bow_* across caller streams
+  // streams of the launches that may set `err` (top-2, SearchByBoW, SearchLocalPoints, RefreshMapPoints, PoseOptimization, Sim3Solver, Initializer, OptimizeSim3)
   StreamMarks errm;
   // staging for the synchronous entry points
   DeviceBuf stage;
@@ -218,7 +220,7 @@ int orbm_destroy(orbm_handle m) {
   m->errm.release();
   // the buffers go before the stream, not with the handle after it
   for (DeviceBuf* b : {&m->init_ws, &m->host_init_ws, &m->err, &m->stereo_sad, &m->bow_hist, &m->bow_rec, &m->pose_picks,
-                       &m->view_ws, &m->refresh_ws, &m->po_ws, &m->sim3_ws, &m->sim3_tab, &m->initz_ws, &m->stage})
+                       &m->view_ws, &m->refresh_ws, &m->po_ws, &m->sim3_ws, &m->sim3_tab, &m->initz_ws, &m->os3_ws, &m->stage})
     b->release();
   m->h_stage.release();
   if (m->stream) (void)hipStreamDestroy(m->stream);
@@ -1434,6 +1436,178 @@ int orbm_sim3_ransac(orbm_handle m, const orbx_kp* kps1, int n1, const orbx_kp* 
   return ORBX_OK;
 }
 
+// ------------------------------------------------- Optimizer::OptimizeSim3
+namespace {
+int optsim3_check(const orbx_kp* kps1, int n1, const orbx_kp* kps2, int n2, const orbm_map_point_world* mps1,
+                  const orbm_map_point_world* mps2, const orbm_camera* cam1, const orbm_camera* cam2,
+                  const int* match12, const int* found12, const int* found21, const float* inv_sigma2, int nlevels,
+                  const float* s12, const float* R12, const float* t12, float th2) {
+  if (n1 < 0 || n2 < 0 || !cam1 || !cam2 || !inv_sigma2 || nlevels < 1 || nlevels > kMaxLevels || !s12 || !R12 ||
+      !t12 || !(th2 >= 0.0f) || (n1 && (!kps1 || !mps1 || !match12)) || (n2 && (!kps2 || !mps2)) ||
+      (found12 != nullptr) != (found21 != nullptr))
+    return g_merr.fail(ORBX_EINVAL, "bad argument");
+  return ORBX_OK;
+}
+}  // namespace
+
+int orbm_optimize_sim3_host(const orbx_kp* kps1, int n1, const orbx_kp* kps2, int n2, const orbm_map_point_world* mps1,
+                            const orbm_map_point_world* mps2, const orbm_camera* cam1, const orbm_camera* cam2,
+                            const int* match12, const uint8_t* inlier, const int* found12, const int* found21,
+                            const float* inv_sigma2, int nlevels, const float* s12, const float* R12,
+                            const float* t12, float th2, int fix_scale, int* match12_out, double* S12, float* Scw,
+                            orbm_pose* pose, orbm_optsim3_result* result, double* lin, int* status) {
+  int rc;
+  if ((rc = optsim3_check(kps1, n1, kps2, n2, mps1, mps2, cam1, cam2, match12, found12, found21, inv_sigma2, nlevels,
+                          s12, R12, t12, th2)))
+    return rc;
+  // found lists of an empty keyframe may be absent: nothing is read from them
+  OptSim3Args A{};
+  A.kps1 = kps1;
+  A.kps2 = kps2;
+  A.mps1 = mps1;
+  A.mps2 = mps2;
+  A.cam1 = cam1;
+  A.cam2 = cam2;
+  A.match12 = match12;
+  A.inlier = inlier;
+  A.found12 = found12;
+  A.found21 = found21;
+  A.inv_sigma2 = inv_sigma2;
+  A.nlevels = nlevels;
+  A.s12 = s12;
+  A.R12 = R12;
+  A.t12 = t12;
+  A.th2 = th2;
+  A.fix_scale = fix_scale;
+  A.pairs = 1;
+  A.match12_out = match12_out;
+  A.S12 = S12;
+  A.Scw = Scw;
+  A.pose = pose;
+  A.result = result;
+  A.lin = lin;
+  return optimize_sim3_host(A, n1, n2, status);
+}
+
+int orbm_optimize_sim3_batch(orbm_handle m, const orbx_kp* d_kps1, const int* d_n1, const orbx_kp* d_kps2,
+                             const int* d_n2, int kp_pitch, const orbm_map_point_world* d_mps1,
+                             const orbm_map_point_world* d_mps2, int mp_pitch, const orbm_camera* d_cam1,
+                             const orbm_camera* d_cam2, const int* d_match12, const uint8_t* d_inlier,
+                             const int* d_found12, const int* d_found21, const float* inv_sigma2, int nlevels,
+                             const float* d_s12, const float* d_R12, const float* d_t12, float th2, int fix_scale,
+                             int pairs, int* d_match12_out, double* d_S12, float* d_Scw, orbm_pose* d_pose,
+                             orbm_optsim3_result* d_result, double* d_lin, void* stream) {
+  if (!m || !d_kps1 || !d_n1 || !d_kps2 || !d_n2 || !d_mps1 || !d_mps2 || !d_cam1 || !d_cam2 || !d_match12 ||
+      !inv_sigma2 || !d_s12 || !d_R12 || !d_t12 || !(th2 >= 0.0f) || pairs < 1 || kp_pitch < 1 ||
+      mp_pitch < kp_pitch || nlevels < 1 || nlevels > kMaxLevels || (d_found12 != nullptr) != (d_found21 != nullptr))
+    return g_merr.fail(ORBX_EINVAL, "bad argument");
+  if (kp_pitch > m->max_kps)
+    return g_merr.fail(ORBX_ECAPACITY, "kp_pitch %d above the handle's max_kps %d", kp_pitch, m->max_kps);
+  HIP_OK(g_merr, hipSetDevice(m->device));
+  hipStream_t s = (hipStream_t)stream;
+  const size_t need = optsim3_ws_bytes(kp_pitch, pairs);
+  if (need) {
+    // the workspace is the handle's: after its last user, whatever its stream
+    if (m->ws.before(s)) return g_merr.fail(ORBX_EDEVICE, "stream wait on the workspace failed");
+    if (m->os3_ws.n < need) {
+      if (m->ws.ev) HIP_OK(g_merr, hipEventSynchronize(m->ws.ev));
+      if (m->os3_ws.reserve(need) != hipSuccess) return g_merr.fail(ORBX_ENOMEM, "OptimizeSim3 workspace");
+    }
+  }
+  OptSim3Args A{};
+  A.kps1 = d_kps1;
+  A.kps2 = d_kps2;
+  A.n1 = d_n1;
+  A.n2 = d_n2;
+  A.kp_pitch = kp_pitch;
+  A.mp_pitch = mp_pitch;
+  A.mps1 = d_mps1;
+  A.mps2 = d_mps2;
+  A.cam1 = d_cam1;
+  A.cam2 = d_cam2;
+  A.match12 = d_match12;
+  A.inlier = d_inlier;
+  A.found12 = d_found12;
+  A.found21 = d_found21;
+  A.inv_sigma2 = inv_sigma2;
+  A.nlevels = nlevels;
+  A.s12 = d_s12;
+  A.R12 = d_R12;
+  A.t12 = d_t12;
+  A.th2 = th2;
+  A.fix_scale = fix_scale;
+  A.pairs = pairs;
+  A.match12_out = d_match12_out;
+  A.S12 = d_S12;
+  A.Scw = d_Scw;
+  A.pose = d_pose;
+  A.result = d_result;
+  A.lin = d_lin;
+  A.err = m->err.as<int>();
+  if (launch_optimize_sim3(A, need ? m->os3_ws.p : nullptr, stream))
+    return g_merr.fail(ORBX_EDEVICE, "OptimizeSim3 launch: %s", hipGetErrorString(hipGetLastError()));
+  if ((need && m->ws.after(s)) || m->errm.mark(s)) return g_merr.fail(ORBX_EDEVICE, "event record failed");
+  return ORBX_OK;
+}
+
+int orbm_optimize_sim3(orbm_handle m, const orbx_kp* kps1, int n1, const orbx_kp* kps2, int n2,
+                       const orbm_map_point_world* mps1, const orbm_map_point_world* mps2, const orbm_camera* cam1,
+                       const orbm_camera* cam2, const int* match12, const uint8_t* inlier, const int* found12,
+                       const int* found21, const float* inv_sigma2, int nlevels, const float* s12, const float* R12,
+                       const float* t12, float th2, int fix_scale, int* match12_out, double* S12, float* Scw,
+                       orbm_pose* pose, orbm_optsim3_result* result, double* lin) {
+  int rc;
+  if (!m) return g_merr.fail(ORBX_EINVAL, "bad argument");
+  if ((rc = optsim3_check(kps1, n1, kps2, n2, mps1, mps2, cam1, cam2, match12, found12, found21, inv_sigma2, nlevels,
+                          s12, R12, t12, th2)))
+    return rc;
+  if (std::max(n1, n2) > m->max_kps)
+    return g_merr.fail(ORBX_ECAPACITY, "%d keypoints above the handle's max_kps %d", std::max(n1, n2), m->max_kps);
+  HIP_OK(g_merr, hipSetDevice(m->device));
+  const size_t kp = std::max(std::max(n1, n2), 1);
+  Stage st(m);
+  auto dk1 = st.slot<orbx_kp>(kp);
+  auto dk2 = st.slot<orbx_kp>(kp);
+  auto dn = st.slot<int>(2);
+  auto dm1 = st.slot<orbm_map_point_world>(kp);
+  auto dm2 = st.slot<orbm_map_point_world>(kp);
+  auto dc = st.slot<orbm_camera>(2);
+  auto d12 = st.slot<int>(kp);
+  auto din = st.slot<uint8_t>(kp);
+  auto df12 = st.slot<int>(kp);
+  auto df21 = st.slot<int>(kp);
+  auto dsrt = st.slot<float>(13);
+  auto dout = st.slot<int>(kp);
+  auto dS = st.slot<double>(8);
+  auto dScw = st.slot<float>(12);
+  auto dpose = st.slot<orbm_pose>(1);
+  auto dres = st.slot<orbm_optsim3_result>(1);
+  auto dlin = st.slot<double>(kOs3Sums);
+  const int counts[2] = {n1, n2};
+  const orbm_camera cams[2] = {*cam1, *cam2};
+  float srt[13];
+  srt[0] = *s12;
+  std::memcpy(srt + 1, R12, 9 * sizeof(float));
+  std::memcpy(srt + 10, t12, 3 * sizeof(float));
+  if ((rc = st.reserve()) || (rc = st.up(dk1, kps1, n1)) || (rc = st.up(dk2, kps2, n2)) ||
+      (rc = st.up(dn, counts, 2)) || (rc = st.up(dm1, mps1, n1)) || (rc = st.up(dm2, mps2, n2)) ||
+      (rc = st.up(dc, cams, 2)) || (rc = st.up(d12, match12, n1)) || (rc = st.up(din, inlier, n1)) ||
+      (rc = st.up(df12, found12, n1)) || (rc = st.up(df21, found21, n2)) ||
+      (rc = st.up(dsrt, (const float*)srt, 13)) ||
+      (rc = orbm_optimize_sim3_batch(m, dk1, dn, dk2, (int*)dn + 1, (int)kp, dm1, dm2, (int)kp, dc,
+                                     (orbm_camera*)dc + 1, d12, inlier ? (uint8_t*)din : nullptr,
+                                     found12 ? (int*)df12 : nullptr, found21 ? (int*)df21 : nullptr, inv_sigma2,
+                                     nlevels, dsrt, (float*)dsrt + 1, (float*)dsrt + 10, th2, fix_scale, 1,
+                                     match12_out ? (int*)dout : nullptr, dS, dScw, dpose, dres,
+                                     lin ? (double*)dlin : nullptr, st.st)) ||
+      (match12_out && (rc = st.down(match12_out, dout, n1))) || (S12 && (rc = st.down(S12, dS, 8))) ||
+      (Scw && (rc = st.down(Scw, dScw, 12))) || (pose && (rc = st.down(pose, dpose, 1))) ||
+      (result && (rc = st.down(result, dres, 1))) || (lin && (rc = st.down(lin, dlin, kOs3Sums))) ||
+      (rc = st.finish()))
+    return rc;
+  return ORBX_OK;
+}
+
 // ---------------------------------------------------------------- Initializer
 namespace {
 int initz_check(const orbx_kp* kps1, int n1, const orbx_kp* kps2, int n2, const int* matches12, const orbm_camera* cam,
@@ -1748,14 +1922,8 @@ int orbm_prepare_pose(int mode, const orbm_camera* cam, const float* Tlw, int mo
     return g_merr.fail(ORBX_EINVAL, "bad argument");
   float Rt[12];
   if (mode == ORBM_PROJ_SIM3 || mode == ORBM_PROJ_FUSE_SIM3) {
-    // scw = sqrt(sRcw.row(0).dot(sRcw.row(0))); Rcw = sRcw/scw; tcw = t/scw
-    // (src/ORBmatcher.cc:298-303, 986-991): Mat::dot in double, Mat / s = convertTo(1/s)
-    const float* S = cam->Tcw;
-    const double d = (double)S[0] * S[0] + (double)S[1] * S[1] + (double)S[2] * S[2];
-    const float scw = (float)std::sqrt(d);
-    if (!(scw > 0)) return g_merr.fail(ORBX_EINVAL, "Scw has a zero scale");
-    const float a = (float)(1.0 / (double)scw);
-    for (int k = 0; k < 12; ++k) Rt[k] = S[k] * a + 0.0f;
+    // Rcw = sRcw/scw, tcw = t/scw (orbx_posemath.cuh)
+    if (!(rt_from_scw(cam->Tcw, Rt) > 0)) return g_merr.fail(ORBX_EINVAL, "Scw has a zero scale");
   } else {
     for (int k = 0; k < 12; ++k) Rt[k] = cam->Tcw[k];
   }

@@ -68,6 +68,19 @@ __host__ __device__ inline void pose_from_rt(const orbm_camera& cam, const float
   for (int k = 0; k < 12; ++k) p->Rt2[k] = 0.0f;
 }
 
+// The 3x4 transform of the Sim3 overloads from Scw (src/ORBmatcher.cc:298-303,
+// 986-991): scw = sqrt(sRcw.row(0).dot(sRcw.row(0))), Rcw = sRcw/scw, tcw =
+// t/scw; Mat::dot in double, Mat / s = convertTo(1/s). orbm_prepare_pose on the
+// host, the Sim3 refinement's orbm_pose on the device. Returns scw.
+__host__ __device__ inline float rt_from_scw(const float* S, float* Rt) {
+  const double d = pm_dadd(pm_dadd(pm_dmul((double)S[0], (double)S[0]), pm_dmul((double)S[1], (double)S[1])),
+                           pm_dmul((double)S[2], (double)S[2]));
+  const float scw = pm_d2f(pm_dsqrt(d));
+  const float a = pm_d2f(pm_ddiv(1.0, (double)scw));
+  for (int k = 0; k < 12; ++k) Rt[k] = pm_fadd(pm_fmul(S[k], a), 0.0f);
+  return scw;
+}
+
 // cv::norm (NORM_L2) of 3 floats: sqrt of the double sum of squares
 __host__ __device__ inline float norm3(float a, float b, float c) {
   const double s = pm_dadd(pm_dadd(pm_dmul((double)a, (double)a), pm_dmul((double)b, (double)b)),

@@ -20,9 +20,11 @@
 // normalize) follow Eigen 3's formulas; where Eigen's evaluation order is not
 // visible in the reference tree the order here is left to right.
 //
-// The solve itself (po_run) is written once, over a context that supplies the
-// three sums over the edges: the kernel reduces them lane -> wave ->
-// workgroup, the host entry adds edge after edge in keypoint order.
+// The solve itself (po_run, and the Levenberg-Marquardt loop lm_optimize under
+// it that orbx_optsim3.cuh runs over 7 unknowns) is written once, over a
+// context that supplies the three sums over the edges: the kernel reduces them
+// lane -> wave -> workgroup, the host entry adds edge after edge in keypoint
+// order.
 #pragma once
 #include <cfloat>
 
@@ -246,9 +248,7 @@ __host__ __device__ inline double po_edge_chi2(const PoCam& c, const PoPose& p, 
 // RobustKernelHuber::robustify (robust_kernel_impl.cpp:78-91): delta is
 // (float)sqrt(5.991) or (float)sqrt(7.815) widened, dsqr the float of its
 // square (robust_kernel_impl.h:84). rho[2] is not used (robustInformation).
-__host__ __device__ inline void po_huber(bool stereo, double e, double* rho0, double* rho1) {
-  const double delta = (double)pm_d2f(pm_dsqrt(stereo ? 7.815 : 5.991));  // deltaStereo / deltaMono, :368-369
-  const double dsqr = (double)pm_d2f(delta * delta);
+__host__ __device__ inline void lm_huber(double delta, double dsqr, double e, double* rho0, double* rho1) {
   if (e <= dsqr) {
     *rho0 = e;
     *rho1 = 1.0;
@@ -257,6 +257,10 @@ __host__ __device__ inline void po_huber(bool stereo, double e, double* rho0, do
     *rho0 = 2 * sqrte * delta - dsqr;
     *rho1 = delta / sqrte;
   }
+}
+__host__ __device__ inline void po_huber(bool stereo, double e, double* rho0, double* rho1) {
+  const double delta = (double)pm_d2f(pm_dsqrt(stereo ? 7.815 : 5.991));  // deltaStereo / deltaMono, :368-369
+  lm_huber(delta, (double)pm_d2f(delta * delta), e, rho0, rho1);
 }
 
 // one edge's term of activeRobustChi2 at pose p
@@ -323,36 +327,138 @@ __host__ __device__ inline bool po_is_outlier(const PoEdge& e, double chi2) {
   return (e.tag & kPoStereo) ? c > 7.815f : c > 5.991f;
 }
 
-// LinearSolverDense::solve on (H + lambda I) x = b: LDL^T without pivoting
-// (Eigen's pivots; the signs of D are the same by inertia). A negative pivot
-// is Eigen's !isPositive(): false, x untouched. H: upper triangle, row by row.
-__host__ __device__ inline bool po_ldlt_solve(const double* H, double lambda, const double* b, double* x) {
-  double A[6][6], D[6], y[6];
+// LinearSolverDense::solve on (H + lambda I) x = b for N unknowns: LDL^T
+// without pivoting (Eigen's pivots; the signs of D are the same by inertia). A
+// negative pivot is Eigen's !isPositive(): false, x untouched. H: upper
+// triangle, row by row.
+template <int N>
+__host__ __device__ inline bool lm_ldlt_solve(const double* H, double lambda, const double* b, double* x) {
+  double A[N][N], D[N], y[N];
   int k = 0;
-  for (int r = 0; r < 6; ++r)
-    for (int c = r; c < 6; ++c, ++k) A[c][r] = H[k] + ((r == c) ? lambda : 0.0);  // lower triangle
-  for (int j = 0; j < 6; ++j) {
+#pragma unroll
+  for (int r = 0; r < N; ++r)
+#pragma unroll
+    for (int c = r; c < N; ++c, ++k) A[c][r] = H[k] + ((r == c) ? lambda : 0.0);  // lower triangle
+#pragma unroll
+  for (int j = 0; j < N; ++j) {
     double d = A[j][j];
+#pragma unroll
     for (int m = 0; m < j; ++m) d = d - A[j][m] * A[j][m] * D[m];
     if (d < 0) return false;
     D[j] = d;
-    for (int i = j + 1; i < 6; ++i) {
+#pragma unroll
+    for (int i = j + 1; i < N; ++i) {
       double s = A[i][j];
+#pragma unroll
       for (int m = 0; m < j; ++m) s = s - A[i][m] * A[j][m] * D[m];
       A[i][j] = s / d;
     }
   }
-  for (int i = 0; i < 6; ++i) {
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
     double s = b[i];
+#pragma unroll
     for (int m = 0; m < i; ++m) s = s - A[i][m] * y[m];
     y[i] = s;
   }
-  for (int i = 5; i >= 0; --i) {
+#pragma unroll
+  for (int i = N - 1; i >= 0; --i) {
     double s = y[i] / D[i];
-    for (int m = i + 1; m < 6; ++m) s = s - A[m][i] * x[m];
+#pragma unroll
+    for (int m = i + 1; m < N; ++m) s = s - A[m][i] * x[m];
     x[i] = s;
   }
   return true;
+}
+
+// the vertex's oplus as lm_optimize applies it; orbx_optsim3.cuh overloads it for its Sim3 vertex
+template <class Ctx>
+__host__ __device__ inline void lm_oplus(Ctx&, const double* x, PoPose* est) {
+  po_oplus(x, est);
+}
+
+// SparseOptimizer::optimize(iterations) on one vertex of N unknowns, one
+// OptimizationAlgorithmLevenberg::solve per iteration, continuing from *est.
+// Ctx supplies over its active edges
+//   void linearise(const Est&, bool robust, double acc[N(N+1)/2 + N + 1])
+//     the upper triangle of H row by row, the negated b, the robust chi2
+//     (computeActiveErrors, activeRobustChi2, buildSystem)
+//   double robust_chi2(const Est&, bool robust)
+// and lm_oplus(ctx, x, Est*) applies an update. *err_est follows the estimate
+// the edges' _error was last computed at: a rejected trial restores the
+// estimate, not the errors. Lambda, ni and the stall counter start afresh at
+// iteration 0.
+template <int N, class Est, class Ctx>
+__host__ __device__ inline void lm_optimize(Ctx& ctx, int iterations, bool robust, Est* est_io, Est* err_est,
+                                            int* trials, int* rejected) {
+  constexpr int kB = N * (N + 1) / 2, kChi = kB + N;
+  Est est = *est_io;
+  double lambda = 0, ni = 2;
+  int nStop = 0;
+  double x[N];
+#pragma unroll
+  for (int k = 0; k < N; ++k) x[k] = 0;
+  for (int i = 0; i < iterations; ++i) {
+    double acc[kChi + 1];
+    ctx.linearise(est, robust, acc);  // computeActiveErrors, activeRobustChi2, buildSystem
+    *err_est = est;
+    double currentChi = acc[kChi], tempChi = currentChi;
+    const double iniChi = currentChi;
+    double b[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) b[k] = -acc[kB + k];
+    if (i == 0) {  // computeLambdaInit: tau * max |H_jj|
+      double maxDiagonal = 0.;
+      int k = 0;
+#pragma unroll
+      for (int r = 0; r < N; k += N - r, ++r) {
+        const double a = fabs(acc[k]);
+        maxDiagonal = (a < maxDiagonal) ? maxDiagonal : a;  // std::max(fabs(hessian(j,j)), maxDiagonal)
+      }
+      lambda = 1e-5 * maxDiagonal;
+      ni = 2;
+      nStop = 0;
+    }
+    double rho = 0;
+    int qmax = 0;
+    do {
+      const Est backup = est;  // push
+      const bool ok2 = lm_ldlt_solve<N>(acc, lambda, b, x);
+      lm_oplus(ctx, x, &est);  // update(x): after a failed solve x is the previous one
+      tempChi = ctx.robust_chi2(est, robust);
+      *err_est = est;
+      if (!ok2) tempChi = DBL_MAX;
+      rho = (currentChi - tempChi);
+      double scale = 0.;  // computeScale
+#pragma unroll
+      for (int k = 0; k < N; ++k) scale += x[k] * (lambda * x[k] + b[k]);
+      scale += 1e-3;
+      rho /= scale;
+      ++*trials;
+      if (rho > 0 && __builtin_isfinite(tempChi)) {  // last step was good
+        const double c = 2 * rho - 1;
+        double alpha = 1. - c * c * c;
+        alpha = (2. / 3. < alpha) ? 2. / 3. : alpha;                 // std::min(alpha, _goodStepUpperScale)
+        const double scaleFactor = (1. / 3. < alpha) ? alpha : 1. / 3.;  // std::max(_goodStepLowerScale, alpha)
+        lambda *= scaleFactor;
+        ni = 2;
+        currentChi = tempChi;
+      } else {
+        lambda *= ni;
+        ni *= 2;
+        est = backup;  // pop: the estimate is restored, the edges' errors are not
+        ++*rejected;
+      }
+      qmax++;
+    } while (rho < 0 && qmax < 10);
+    if (qmax == 10 || rho == 0) break;  // Terminate
+    if ((iniChi - currentChi) * 1e3 < iniChi)  // the added stop rule
+      nStop++;
+    else
+      nStop = 0;
+    if (nStop >= 3) break;
+  }
+  *est_io = est;
 }
 
 // what po_run reports beside the pose
@@ -380,68 +486,8 @@ __host__ __device__ inline void po_run(Ctx& ctx, const PoPose& T0, int n_initial
     est = T0;  // vSE3->setEstimate(toSE3Quat(pFrame->mTcw)), :469
     PoPose err_pose = T0;
     const bool robust = it < 3;  // setRobustKernel(0) after the third classification
-    if (n_initial - nBad > 0) {  // else optimize() finds no vertex to optimise and returns
-      double lambda = 0, ni = 2;
-      int nStop = 0;
-      double x[6] = {0, 0, 0, 0, 0, 0};
-      for (int i = 0; i < 10; ++i) {  // SparseOptimizer::optimize(10), one OptimizationAlgorithmLevenberg::solve each
-        double acc[kPoSums];
-        ctx.linearise(est, robust, acc);  // computeActiveErrors, activeRobustChi2, buildSystem
-        err_pose = est;
-        double currentChi = acc[kPoChi], tempChi = currentChi;
-        const double iniChi = currentChi;
-        double b[6];
-        for (int k = 0; k < 6; ++k) b[k] = -acc[kPoB + k];
-        if (i == 0) {  // computeLambdaInit: tau * max |H_jj|
-          double maxDiagonal = 0.;
-          int k = 0;
-          for (int r = 0; r < 6; k += 6 - r, ++r) {
-            const double a = fabs(acc[k]);
-            maxDiagonal = (a < maxDiagonal) ? maxDiagonal : a;  // std::max(fabs(hessian(j,j)), maxDiagonal)
-          }
-          lambda = 1e-5 * maxDiagonal;
-          ni = 2;
-          nStop = 0;
-        }
-        double rho = 0;
-        int qmax = 0;
-        do {
-          const PoPose backup = est;  // push
-          const bool ok2 = po_ldlt_solve(acc, lambda, b, x);
-          po_oplus(x, &est);  // update(x): after a failed solve x is the previous one
-          tempChi = ctx.robust_chi2(est, robust);
-          err_pose = est;
-          if (!ok2) tempChi = DBL_MAX;
-          rho = (currentChi - tempChi);
-          double scale = 0.;  // computeScale
-          for (int k = 0; k < 6; ++k) scale += x[k] * (lambda * x[k] + b[k]);
-          scale += 1e-3;
-          rho /= scale;
-          ++st->trials;
-          if (rho > 0 && __builtin_isfinite(tempChi)) {  // last step was good
-            const double c = 2 * rho - 1;
-            double alpha = 1. - c * c * c;
-            alpha = (2. / 3. < alpha) ? 2. / 3. : alpha;                 // std::min(alpha, _goodStepUpperScale)
-            const double scaleFactor = (1. / 3. < alpha) ? alpha : 1. / 3.;  // std::max(_goodStepLowerScale, alpha)
-            lambda *= scaleFactor;
-            ni = 2;
-            currentChi = tempChi;
-          } else {
-            lambda *= ni;
-            ni *= 2;
-            est = backup;  // pop: the estimate is restored, the edges' errors are not
-            ++st->rejected;
-          }
-          qmax++;
-        } while (rho < 0 && qmax < 10);
-        if (qmax == 10 || rho == 0) break;  // Terminate
-        if ((iniChi - currentChi) * 1e3 < iniChi)  // the added stop rule
-          nStop++;
-        else
-          nStop = 0;
-        if (nStop >= 3) break;
-      }
-    }
+    if (n_initial - nBad > 0)  // else optimize() finds no vertex to optimise and returns
+      lm_optimize<6>(ctx, 10, robust, &est, &err_pose, &st->trials, &st->rejected);  // SparseOptimizer::optimize(10)
     nBad = ctx.classify(est, err_pose);
     ++st->rounds;
     if (n_initial < 10) break;  // optimizer.edges().size() < 10, :532

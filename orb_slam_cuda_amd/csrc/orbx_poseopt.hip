@@ -9,8 +9,8 @@
 // with a fixed DPP tree, and every thread then adds the waves' partial sums
 // from LDS in wave order. So a sum's bits depend on the edges' order in the
 // frame alone, not on the batch, the slot or the run, and no floating-point
-// atomic is involved. Two LDS buffers alternate, so a reduction costs one
-// barrier. The 6x6 solve, exp and the lambda logic run in every thread on the
+// atomic is involved (BlockSum, orbx_wave.cuh). Two LDS buffers alternate, so a
+// reduction costs one barrier. The 6x6 solve, exp and the lambda logic run in every thread on the
 // same reduced values (po_run): nobody waits for a thread 0 and a broadcast.
 //
 // A frame pitch above kPoLdsEdges keeps its edge records in a workspace in
@@ -26,76 +26,19 @@ namespace orbx {
 
 namespace {
 
-template <int CTRL, int ROW_MASK = 0xf>
-__device__ __forceinline__ double dpp_d(double v) {
-  const long long b = __double_as_longlong(v);
-  const int lo = dpp_i<CTRL, ROW_MASK>(0, (int)(uint32_t)b);
-  const int hi = dpp_i<CTRL, ROW_MASK>(0, (int)(uint32_t)((unsigned long long)b >> 32));
-  return __longlong_as_double((long long)(((unsigned long long)(uint32_t)hi << 32) | (uint32_t)lo));
-}
-
-// the sum of v over the 64 lanes in wave_sum_dpp's fixed order, wave-uniform
-__device__ __forceinline__ double wave_sum_f64(double v) {
-  v += dpp_d<kDppQuad1032>(v);
-  v += dpp_d<kDppQuad2301>(v);
-  v += dpp_d<kDppHalfMirror>(v);
-  v += dpp_d<kDppMirror>(v);
-  v += dpp_d<kDppBcast15, 0xa>(v);
-  v += dpp_d<kDppBcast31, 0xc>(v);
-  const long long b = __double_as_longlong(v);
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)b, 63);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((unsigned long long)b >> 32), 63);
-  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-
-// LDS of the reductions: two alternating buffers of the waves' partial sums
-template <int W>
-struct PoShared {
-  double part[2][W][kPoSums];
-  int ipart[2][W];
-};
-
 template <int T, class EdgePtr>
 struct DeviceCtx {
   static constexpr int W = T / 64;
   EdgePtr E;
   int ne;
   PoCam cam;
-  PoShared<W>* sh;
-  int parity = 0, iparity = 0;
+  BlockSum<W, kPoSums> red;  // the reductions' LDS and order (orbx_wave.cuh)
 
-  // v[0..N) summed over the workgroup, the same bits in every thread
   template <int N>
   __device__ void block_sum(double* v) {
-#pragma unroll
-    for (int k = 0; k < N; ++k) v[k] = wave_sum_f64(v[k]);
-    if (W == 1) return;
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-      for (int k = 0; k < N; ++k) sh->part[parity][wave][k] = v[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-      double s = sh->part[parity][0][k];
-#pragma unroll
-      for (int w = 1; w < W; ++w) s += sh->part[parity][w][k];
-      v[k] = s;
-    }
-    parity ^= 1;
+    red.template sum<N>(v);
   }
-  __device__ int block_sum_int(int v) {
-    v = wave_sum_dpp(v);
-    if (W == 1) return v;
-    if ((threadIdx.x & 63) == 0) sh->ipart[iparity][threadIdx.x >> 6] = v;
-    __syncthreads();
-    int s = 0;
-#pragma unroll
-    for (int w = 0; w < W; ++w) s += sh->ipart[iparity][w];
-    iparity ^= 1;
-    return s;
-  }
+  __device__ int block_sum_int(int v) { return red.sum_int(v); }
 
   __device__ void linearise(const PoPose& est, bool robust, double* acc) {
 #pragma unroll
@@ -153,7 +96,7 @@ template <int T, bool SPILL>
 __global__ __launch_bounds__(T) void pose_optimization_kernel(const PoArgs A) {
   constexpr int W = T / 64;
   extern __shared__ __align__(16) unsigned char po_lds[];
-  __shared__ PoShared<W> sh;
+  __shared__ BlockSumLds<W, kPoSums> sh;
   __shared__ int scan[2][W];
   const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int n = A.n[f];
@@ -222,7 +165,7 @@ __global__ __launch_bounds__(T) void pose_optimization_kernel(const PoArgs A) {
   ctx.E = E;
   ctx.ne = ne;
   ctx.cam = PoCam{(double)cam.fx, (double)cam.fy, (double)cam.cx, (double)cam.cy, (double)cam.mbf};
-  ctx.sh = &sh;
+  ctx.red.sh = &sh;
 
   PoStats st{0, 0, 0, 0};
   float Tout[12];

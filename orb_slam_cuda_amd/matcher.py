@@ -926,6 +926,56 @@ class ORBmatcher:
         self.last_sim3_poses = poses
         return (srt[0], srt[1:10].reshape(3, 3).copy(), srt[10:13].copy()), inlier[:n1], r
 
+    def OptimizeSim3(self, kps1, mps1, cam1, kps2, mps2, cam2, match12, inv_sigma2, s12, R12, t12, *, inlier=None,
+                     found12=None, found21=None, th2=10.0, fix_scale=False, want_lin=False, host=False):
+        """Optimizer::OptimizeSim3 (src/Optimizer.cc:1190-1385) in one device round trip (orbm_optimize_sim3),
+        or on the host alone with host=True (orbm_optimize_sim3_host). kps1 / kps2: KP_DTYPE (mvKeysUn); mps1 /
+        mps2: MAP_POINT_WORLD_DTYPE, one per keypoint; cam1 / cam2: _lib.camera(...) of each keyframe with its
+        Tcw; inv_sigma2 = mvInvLevelSigma2; (s12, R12, t12): the RANSAC's estimate. vpMatches1 is match12 (int32
+        per keypoint of KF1, the keypoint of KF2 or -1) where inlier (uint8 per keypoint, None = all) is set,
+        else the mutual agreement of found12 / found21 (the two SearchBySim3 directions, both or neither).
+        Returns (nIn, match12_out, S12, Scw, result): vpMatches1 as the function leaves it (int32, -1 where
+        rejected), g2oS12 as 8 doubles (qx, qy, qz, qw, tx, ty, tz, s), Scw (3, 4) float32 of gScm * gSmw and an
+        OPTSIM3_RESULT_DTYPE record. The orbm_pose for SearchByProjection(pKF, Scw, ...) stays in
+        self.last_optsim3_pose, the first linearisation (36 doubles) in self.last_optsim3_lin with want_lin.
+        Entries left out for an index or octave out of range set bit 8192 of status() (host=True:
+        self.last_host_status)."""
+        kps1 = np.ascontiguousarray(kps1, KP_DTYPE)
+        kps2 = np.ascontiguousarray(kps2, KP_DTYPE)
+        mps1 = np.ascontiguousarray(mps1, MAP_POINT_WORLD_DTYPE)
+        mps2 = np.ascontiguousarray(mps2, MAP_POINT_WORLD_DTYPE)
+        n1, n2 = len(kps1), len(kps2)
+        m12 = np.ascontiguousarray(match12, np.int32)
+        inl = None if inlier is None else np.ascontiguousarray(inlier, np.uint8)
+        f12 = None if found12 is None else np.ascontiguousarray(found12, np.int32)
+        f21 = None if found21 is None else np.ascontiguousarray(found21, np.int32)
+        if (f12 is None) != (f21 is None):
+            raise _lib.OrbxError(_lib.ORBX_EINVAL, "found12 and found21 go together")
+        if (len(mps1) != n1 or len(mps2) != n2 or len(m12) != n1 or (inl is not None and len(inl) != n1)
+                or (f12 is not None and (len(f12) != n1 or len(f21) != n2))):
+            raise _lib.OrbxError(_lib.ORBX_EINVAL, "one map point per keypoint, one list entry per keypoint")
+        sig = np.ascontiguousarray(inv_sigma2, np.float32)
+        srt = np.concatenate([[s12], np.asarray(R12, np.float32).reshape(9),
+                              np.asarray(t12, np.float32).reshape(3)]).astype(np.float32)
+        out = np.full(max(n1, 1), -1, np.int32)
+        S12 = np.zeros(8, np.float64)
+        Scw = np.zeros(12, np.float32)
+        pose = np.zeros(1, _lib.POSE_DTYPE)
+        res = np.zeros(1, _lib.OPTSIM3_RESULT_DTYPE)
+        lin = np.zeros(36, np.float64) if want_lin else None
+        args = (ptr(kps1), n1, ptr(kps2), n2, ptr(mps1), ptr(mps2), C.addressof(cam1), C.addressof(cam2), ptr(m12),
+                ptr(inl), ptr(f12), ptr(f21), ptr(sig), len(sig), ptr(srt[0:1]), ptr(srt[1:10]), ptr(srt[10:13]),
+                C.c_float(th2), int(bool(fix_scale)), ptr(out), ptr(S12), ptr(Scw), ptr(pose), ptr(res), ptr(lin))
+        if host:
+            st = C.c_int(0)
+            check(lib().orbm_optimize_sim3_host(*args, C.byref(st)), matcher=True)
+            self.last_host_status = st.value
+        else:
+            check(lib().orbm_optimize_sim3(self._h, *args), matcher=True)
+        self.last_optsim3_pose = pose
+        self.last_optsim3_lin = lin
+        return int(res[0]["ret"]), out[:n1], S12, Scw.reshape(3, 4), res[0]
+
     def Initialize(self, kps1, kps2, matches12, cam, rand8=None, *, sigma=1.0, max_iterations=200, min_parallax=1.0,
                    min_triangulated=50, want_hyp=False, host=False):
         """Initializer::Initialize (src/Initializer.cc:44-121) with everything under it, in one device round trip

@@ -9,7 +9,8 @@
 //   orbx_shim_driver --version
 //   orbx_shim_driver FRAMES.u8 NFRAMES W H VOC.txt|- OUTDIR
 //   orbx_shim_driver --scene SCENE.bin OUT.bin   (one call of the drop-in classes on a test scene: an ORBmatcher
-//                                 method, PoseOptimization, Sim3Solver, CreateNewMapPoints or Initializer; scene.cc)
+//                                 method, PoseOptimization, Sim3Solver, OptimizeSim3, CreateNewMapPoints or Initializer;
+//                                 scene.cc)
 //   orbx_shim_driver --stereo LEFT.u8 RIGHT.u8 NPAIRS W H BF OUTDIR
 //                                 (stereo Frames, two extraction threads each, + ComputeStereoMatches)
 //   orbx_shim_driver --stereo-rectify LEFT.u8 RIGHT.u8 M1L.f32 M2L.f32 M1R.f32 M2R.f32 NPAIRS W H BF OUTDIR

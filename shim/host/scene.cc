@@ -17,6 +17,7 @@
 //   op 12 Sim3Solver(pKF1, pKF2, vpMatches12, fix), SetRansacParameters, iterate(k)...  LoopClosing.cc:313-340
 //   op 13 CreateNewMapPoints(pKF, vpNeighKFs, bMonocular): the search, triangulation and refresh of LocalMapping.cc:270-483
 //   op 14 Initializer(ReferenceFrame, sigma, iterations), Initialize(CurrentFrame, vMatches12, ...)  Tracking.cc:638-700
+//   op 15 Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale)    LoopClosing.cc:365
 // --scene-latency: the same scene rebuilt per call, only the method call on
 // the host clock (median / p99 over the calls after the warm ones).
 // Scene file: records of [u32 name length][name][u32 dtype 0 u8 / 1 i32 /
@@ -512,6 +513,31 @@ static void run_op(const Scene& s, std::vector<int>& res, double* ms) {
       const cv::Mat R = solver.GetEstimatedRotation(), t = solver.GetEstimatedTranslation();
       for (int k = 0; k < 9; ++k) res.push_back(bits(R.at<float>(k / 3, k % 3)));
       for (int k = 0; k < 3; ++k) res.push_back(bits(t.at<float>(k)));
+      break;
+    }
+    case 15: {  // -> [return value, vpMatches1..., the two words of each of g2oS12's 8 doubles (r, t, s)]
+      auto K1 = keyframe(s, "A", pool);
+      auto K2 = keyframe(s, "B", pool);
+      observe(K1.get(), s, pool);
+      observe(K2.get(), s, pool);
+      std::vector<MapPoint*> m1 = pointers(s, "matched", pool);
+      const auto srt = s.vec<float>("srt");  // s, R (9), t (3): the solver's floats (src/LoopClosing.cc:359-364)
+      double R[9], t[3];
+      for (int k = 0; k < 9; ++k) R[k] = (double)srt[1 + k];
+      for (int k = 0; k < 3; ++k) t[k] = (double)srt[10 + k];
+      g2o::Sim3 S = g2o::Sim3::fromMatrix(R, t, (double)srt[0]);
+      tic();
+      const int n = Optimizer::OptimizeSim3(K1.get(), K2.get(), m1, S, s.f("th2"), s.i("fix_scale") != 0);
+      toc();
+      res.push_back(n);
+      for (MapPoint* p : m1) res.push_back(id_of(p));
+      const double v[8] = {S.r[0], S.r[1], S.r[2], S.r[3], S.t[0], S.t[1], S.t[2], S.s};
+      for (int k = 0; k < 8; ++k) {
+        int w[2];
+        memcpy(w, &v[k], 8);
+        res.push_back(w[0]);
+        res.push_back(w[1]);
+      }
       break;
     }
     case 13: {  // -> [n, per new point: neighbour, idx1, idx2, kind, pKF2 precedes pKF1 in std::map order, the bits of
