@@ -529,16 +529,19 @@ def features_in_area(kps, cells, bounds, x, y, r, minLevel, maxLevel):
     invW = f32(f32(64) / f32(maxX - minX))
     invH = f32(f32(48) / f32(maxY - minY))
     x, y, r = f32(x), f32(y), f32(r)
-    cx0 = max(0, int(math.floor(f32(f32(f32(x - minX) - r) * invW))))
+
+    def to_int(v):  # x86 float -> int of a NaN (a projection at z = 0): INT_MIN
+        return int(v) if math.isfinite(v) else -2 ** 31
+    cx0 = max(0, to_int(np.floor(f32(f32(f32(x - minX) - r) * invW))))
     if cx0 >= 64:
         return []
-    cx1 = min(63, int(math.ceil(f32(f32(f32(x - minX) + r) * invW))))
+    cx1 = min(63, to_int(np.ceil(f32(f32(f32(x - minX) + r) * invW))))
     if cx1 < 0:
         return []
-    cy0 = max(0, int(math.floor(f32(f32(f32(y - minY) - r) * invH))))
+    cy0 = max(0, to_int(np.floor(f32(f32(f32(y - minY) - r) * invH))))
     if cy0 >= 48:
         return []
-    cy1 = min(47, int(math.ceil(f32(f32(f32(y - minY) + r) * invH))))
+    cy1 = min(47, to_int(np.ceil(f32(f32(f32(y - minY) + r) * invH))))
     if cy1 < 0:
         return []
     check = minLevel > 0 or maxLevel >= 0
@@ -568,9 +571,27 @@ def grid_cells(kps, bounds):
     return cells
 
 
-def search_by_projection(kps, desc, uright, bounds, scale, blocked, mps, mpdesc, th, ratio, independent=False):
+def _trace_recs(trace, n):
+    """One record per map point for the projection searches' optional `trace` list: `stage`,
+    where the point ended ("invalid", "depth", "image", "distance", "viewing", "window": the grid
+    window is empty or holds no keypoint in reach, "no candidate": every keypoint in reach is
+    blocked or fails the overload's per-keypoint test, "threshold", "ratio", "matched"), and
+    what was computed before that: `u`, `v`, `rad`, `lvl`, `minL`, `maxL` (the level band as
+    GetFeaturesInArea or the matcher applies it; -1 = open), `area` (GetFeaturesInArea's
+    indices in visiting order), `cands` ((index, distance) of every keypoint compared, in
+    visiting order), `best`, `best2`, `pick`."""
+    recs = [dict(stage="invalid") for _ in range(n)]
+    if trace is not None:
+        trace.extend(recs)
+    return recs
+
+
+def search_by_projection(kps, desc, uright, bounds, scale, blocked, mps, mpdesc, th, ratio, independent=False,
+                         trace=None):
     """ORBmatcher::SearchByProjection(Frame&, vector<MapPoint*>, th) (src/ORBmatcher.cc:45-118).
-    independent=True drops the blocking by earlier points (a test of the test data only)."""
+    independent=True drops the blocking by earlier points (a test of the test data only).
+    trace: see _trace_recs."""
+    recs = _trace_recs(trace, len(mps))
     cells = grid_cells(kps, bounds)
     blk = [bool(b) for b in blocked]
     out = [-1] * len(kps)
@@ -586,6 +607,9 @@ def search_by_projection(kps, desc, uright, bounds, scale, blocked, mps, mpdesc,
             r = f32(r * th)
         rad = f32(r * f32(scale[lvl]))
         idxs = features_in_area(kps, cells, bounds, mp["proj_x"], mp["proj_y"], rad, lvl - 1, lvl)
+        rec = recs[j]
+        rec.update(stage="window" if not idxs else "no candidate", u=f32(mp["proj_x"]), v=f32(mp["proj_y"]),
+                   rad=rad, lvl=lvl, minL=lvl - 1, maxL=lvl, area=list(idxs), cands=[])
         best, bl, best2, bl2, bi = 256, -1, 256, -1, -1
         for i in idxs:
             if blk[i]:
@@ -594,13 +618,18 @@ def search_by_projection(kps, desc, uright, bounds, scale, blocked, mps, mpdesc,
                 if abs(f32(f32(mp["proj_xr"]) - f32(uright[i]))) > rad:
                     continue
             d = hamming(mpdesc[j], desc[i])
+            rec["cands"].append((int(i), d))
             if d < best:
                 best2, best, bl2, bl, bi = best, d, bl, int(kps["octave"][i]), i
             elif d < best2:
                 bl2, best2 = int(kps["octave"][i]), d
+        if rec["cands"]:
+            rec.update(stage="threshold", best=best, best2=best2, lv=bl, lv2=bl2)
         if best <= 100:
             if bl == bl2 and f32(best) > f32(f32(ratio) * f32(best2)):
+                rec["stage"] = "ratio"
                 continue
+            rec.update(stage="matched", pick=int(bi))
             out[bi] = j
             if not independent:
                 blk[bi] = bool(mp["obs_positive"])
@@ -683,8 +712,10 @@ def _cam(cam):
 
 
 def search_by_projection_last_frame(kps, desc, uright, bounds, scale, blocked, cam, Tlw, mps, mpdesc, th, mono,
-                                    check_ori=True):
-    """SearchByProjection(CurrentFrame, LastFrame, th, bMono) (src/ORBmatcher.cc:1328-1470)."""
+                                    check_ori=True, trace=None):
+    """SearchByProjection(CurrentFrame, LastFrame, th, bMono) (src/ORBmatcher.cc:1328-1470).
+    trace: see _trace_recs; matched records also hold `bin`, the rotation histogram bin."""
+    recs = _trace_recs(trace, len(mps))
     fx, fy, cx, cy, mb, mbf, T = _cam(cam)
     cells = grid_cells(kps, bounds)
     minX, maxX, minY, maxY = (f32(b) for b in bounds)
@@ -703,20 +734,22 @@ def search_by_projection_last_frame(kps, desc, uright, bounds, scale, blocked, c
             continue
         xc, yc, zc = _mat_rx_t(T, mp["pos"])
         invzc = f32(1.0 / float(zc)) if zc != 0 else f32(math.copysign(math.inf, float(zc)))
+        rec = recs[i]
+        rec["stage"] = "depth"
         if invzc < 0:
             continue
-        u = f32(f32(f32(fx * xc) * invzc) + cx)
-        v = f32(f32(f32(fy * yc) * invzc) + cy)
+        with np.errstate(invalid="ignore"):
+            u = f32(f32(f32(fx * xc) * invzc) + cx)
+            v = f32(f32(f32(fy * yc) * invzc) + cy)
+        rec.update(stage="image", u=u, v=v)
         if u < minX or u > maxX or v < minY or v > maxY:
             continue
         lo = int(mp["octave"])
         rad = f32(th * f32(scale[lo]))
-        if fwd:
-            idxs = features_in_area(kps, cells, bounds, u, v, rad, lo, -1)
-        elif bwd:
-            idxs = features_in_area(kps, cells, bounds, u, v, rad, 0, lo)
-        else:
-            idxs = features_in_area(kps, cells, bounds, u, v, rad, lo - 1, lo + 1)
+        band = (lo, -1) if fwd else (0, lo) if bwd else (lo - 1, lo + 1)
+        idxs = features_in_area(kps, cells, bounds, u, v, rad, *band)
+        rec.update(stage="window" if not idxs else "no candidate", rad=rad, lvl=lo, minL=band[0], maxL=band[1],
+                   area=list(idxs), cands=[])
         best, bi = 256, -1
         for i2 in idxs:
             if blk[i2]:
@@ -726,22 +759,29 @@ def search_by_projection_last_frame(kps, desc, uright, bounds, scale, blocked, c
                 if abs(f32(ur - f32(uright[i2]))) > rad:
                     continue
             d = hamming(mpdesc[i], desc[i2])
+            rec["cands"].append((int(i2), d))
             if d < best:
                 best, bi = d, i2
+        if rec["cands"]:
+            rec.update(stage="threshold", best=best)
         if best <= 100:
+            rec.update(stage="matched", pick=int(bi))
             out[bi] = i
             blk[bi] = bool(mp["obs_positive"])
             nm += 1
             if check_ori:
-                hist[rot_bin(mp["angle"], kps["angle"][bi])].append(bi)
+                rec["bin"] = rot_bin(mp["angle"], kps["angle"][bi])
+                hist[rec["bin"]].append(bi)
     if check_ori:
         nm = _rot_filter(hist, out, nm)
     return np.array(out, np.int32), nm
 
 
 def search_by_projection_keyframe(kps, desc, bounds, scale, sf, has_mp, cam, mps, mpdesc, th, orb_dist,
-                                  check_ori=True):
-    """SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (src/ORBmatcher.cc:1472-1599)."""
+                                  check_ori=True, trace=None):
+    """SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (src/ORBmatcher.cc:1472-1599).
+    trace: see _trace_recs; matched records also hold `bin`, the rotation histogram bin."""
+    recs = _trace_recs(trace, len(mps))
     fx, fy, cx, cy, mb, mbf, T = _cam(cam)
     cells = grid_cells(kps, bounds)
     minX, maxX, minY, maxY = (f32(b) for b in bounds)
@@ -758,36 +798,50 @@ def search_by_projection_keyframe(kps, desc, bounds, scale, sf, has_mp, cam, mps
             continue
         xc, yc, zc = _mat_rx_t(T, mp["pos"])
         invzc = f32(1.0 / float(zc)) if zc != 0 else f32(math.copysign(math.inf, float(zc)))
-        u = f32(f32(f32(fx * xc) * invzc) + cx)
-        v = f32(f32(f32(fy * yc) * invzc) + cy)
+        with np.errstate(invalid="ignore"):
+            u = f32(f32(f32(fx * xc) * invzc) + cx)
+            v = f32(f32(f32(fy * yc) * invzc) + cy)
+        rec = recs[i]
+        rec.update(stage="image", u=u, v=v)
         if u < minX or u > maxX or v < minY or v > maxY:
             continue
         PO = [f32(f32(mp["pos"][k]) - Ow[k]) for k in range(3)]
         d3 = f32(_norm3(PO))
+        rec.update(stage="distance", dist=d3)
         if d3 < f32(f32(0.8) * f32(mp["min_distance"])) or d3 > f32(f32(1.2) * f32(mp["max_distance"])):
             continue
         lvl = predict_scale(mp["max_distance"], d3, sf, L)
         rad = f32(th * f32(scale[lvl]))
+        idxs = features_in_area(kps, cells, bounds, u, v, rad, lvl - 1, lvl + 1)
+        rec.update(stage="window" if not idxs else "no candidate", rad=rad, lvl=lvl, minL=lvl - 1, maxL=lvl + 1,
+                   area=list(idxs), cands=[])
         best, bi = 256, -1
-        for i2 in features_in_area(kps, cells, bounds, u, v, rad, lvl - 1, lvl + 1):
+        for i2 in idxs:
             if taken[i2]:
                 continue
             d = hamming(mpdesc[i], desc[i2])
+            rec["cands"].append((int(i2), d))
             if d < best:
                 best, bi = d, i2
+        if rec["cands"]:
+            rec.update(stage="threshold", best=best)
         if best <= orb_dist:
+            rec.update(stage="matched", pick=int(bi))
             out[bi] = i
             taken[bi] = True
             nm += 1
             if check_ori:
-                hist[rot_bin(mp["angle"], kps["angle"][bi])].append(bi)
+                rec["bin"] = rot_bin(mp["angle"], kps["angle"][bi])
+                hist[rec["bin"]].append(bi)
     if check_ori:
         nm = _rot_filter(hist, out, nm)
     return np.array(out, np.int32), nm
 
 
-def search_by_projection_sim3(kps, desc, bounds, scale, sf, cam, mps, mpdesc, th, matched=None):
-    """SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) (src/ORBmatcher.cc:290-403)."""
+def search_by_projection_sim3(kps, desc, bounds, scale, sf, cam, mps, mpdesc, th, matched=None, trace=None):
+    """SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) (src/ORBmatcher.cc:290-403).
+    trace: see _trace_recs."""
+    recs = _trace_recs(trace, len(mps))
     fx, fy, cx, cy, mb, mbf, S = _cam(cam)
     cells = grid_cells(kps, bounds)
     minX, maxX, minY, maxY = (f32(b) for b in bounds)
@@ -804,32 +858,45 @@ def search_by_projection_sim3(kps, desc, bounds, scale, sf, cam, mps, mpdesc, th
         if not mp["valid"]:
             continue
         X, Y, Z = _mat_rx_t(T, mp["pos"])
+        rec = recs[i]
+        rec["stage"] = "depth"
         if Z < 0.0:
             continue
-        invz = f32(f32(1) / Z)
-        u = f32(f32(fx * f32(X * invz)) + cx)
-        v = f32(f32(fy * f32(Y * invz)) + cy)
+        with np.errstate(divide="ignore", invalid="ignore"):  # z = 0: inf, then NaN
+            invz = f32(f32(1) / Z)
+            u = f32(f32(fx * f32(X * invz)) + cx)
+            v = f32(f32(fy * f32(Y * invz)) + cy)
+        rec.update(stage="image", u=u, v=v)
         if not (u >= minX and u < maxX and v >= minY and v < maxY):
             continue
         PO = [f32(f32(mp["pos"][k]) - Ow[k]) for k in range(3)]
         dist = f32(_norm3(PO))
+        rec.update(stage="distance", dist=dist)
         if dist < f32(f32(0.8) * f32(mp["min_distance"])) or dist > f32(f32(1.2) * f32(mp["max_distance"])):
             continue
+        rec["stage"] = "viewing"
         if _dot3(PO, mp["normal"]) < 0.5 * float(dist):
             continue
         lvl = predict_scale(mp["max_distance"], dist, sf, L)
         rad = f32(f32(th) * f32(scale[lvl]))
+        idxs = features_in_area(kps, cells, bounds, u, v, rad, -1, -1)
+        rec.update(stage="window" if not idxs else "no candidate", rad=rad, lvl=lvl, minL=lvl - 1, maxL=lvl,
+                   area=list(idxs), cands=[])
         best, bi = 256, -1
-        for idx in features_in_area(kps, cells, bounds, u, v, rad, -1, -1):
+        for idx in idxs:
             if taken[idx]:
                 continue
             o = int(kps["octave"][idx])
             if o < lvl - 1 or o > lvl:
                 continue
             d = hamming(mpdesc[i], desc[idx])
+            rec["cands"].append((int(idx), d))
             if d < best:
                 best, bi = d, idx
+        if rec["cands"]:
+            rec.update(stage="threshold", best=best)
         if best <= 50:
+            rec.update(stage="matched", pick=int(bi))
             out[bi] = i
             taken[bi] = True
             nm += 1
@@ -853,22 +920,33 @@ def _dist_ok(mp, dist):
     return not (dist < f32(f32(0.8) * f32(mp["min_distance"])) or dist > f32(f32(1.2) * f32(mp["max_distance"])))
 
 
-def _kf_best(kps, desc, cells, bounds, u, v, rad, lvl, dmp, init, extra=None):
+def _kf_best(kps, desc, cells, bounds, u, v, rad, lvl, dmp, init, extra=None, rec=None, limit=50):
     best, bi = init, -1
-    for idx in features_in_area(kps, cells, bounds, u, v, rad, -1, -1):
+    idxs = features_in_area(kps, cells, bounds, u, v, rad, -1, -1)
+    rec = {} if rec is None else rec
+    rec.update(stage="window" if not idxs else "no candidate", u=u, v=v, rad=rad, lvl=lvl, minL=lvl - 1, maxL=lvl,
+               area=list(idxs), cands=[])
+    for idx in idxs:
         o = int(kps["octave"][idx])
         if o < lvl - 1 or o > lvl:
             continue
         if extra is not None and not extra(idx):
             continue
         d = hamming(dmp, desc[idx])
+        rec["cands"].append((int(idx), d))
         if d < best:
             best, bi = d, idx
+    if rec["cands"]:
+        rec.update(stage="threshold", best=best)
+        if best <= limit:
+            rec.update(stage="matched", pick=int(bi))
     return best, bi
 
 
-def fuse(kps, desc, uright, bounds, scale, inv_sigma2, sf, cam, mps, mpdesc, th):
-    """Fuse(pKF, vpMapPoints, th) (src/ORBmatcher.cc:825-930), match part."""
+def fuse(kps, desc, uright, bounds, scale, inv_sigma2, sf, cam, mps, mpdesc, th, trace=None):
+    """Fuse(pKF, vpMapPoints, th) (src/ORBmatcher.cc:825-930), match part. trace: see _trace_recs;
+    `chi2` holds (index, e2 * invSigma2, stereo) of every keypoint whose error was tested."""
+    recs = _trace_recs(trace, len(mps))
     fx, fy, cx, cy, mb, bf, T = _cam(cam)
     cells = grid_cells(kps, bounds)
     Ow = _mat_neg_rt_t(T)
@@ -880,17 +958,25 @@ def fuse(kps, desc, uright, bounds, scale, inv_sigma2, sf, cam, mps, mpdesc, th)
         if not mp["valid"]:
             continue
         X, Y, Z = _mat_rx_t(T, mp["pos"])
+        rec = recs[i]
+        rec["stage"] = "depth"
         if Z < f32(0):
             continue
-        invz = f32(f32(1) / Z)
-        u = f32(f32(fx * f32(X * invz)) + cx)
-        v = f32(f32(fy * f32(Y * invz)) + cy)
+        with np.errstate(divide="ignore", invalid="ignore"):  # z = 0: inf, then NaN
+            invz = f32(f32(1) / Z)
+            u = f32(f32(fx * f32(X * invz)) + cx)
+            v = f32(f32(fy * f32(Y * invz)) + cy)
+        rec.update(stage="image", u=u, v=v)
         if not _in_image(u, v, bounds):
             continue
         ur = f32(u - f32(bf * invz))
         PO = [f32(f32(mp["pos"][k]) - Ow[k]) for k in range(3)]
         dist = f32(_norm3(PO))
-        if not _dist_ok(mp, dist) or _dot3(PO, mp["normal"]) < 0.5 * float(dist):
+        rec.update(stage="distance", dist=dist, chi2=[])
+        if not _dist_ok(mp, dist):
+            continue
+        rec["stage"] = "viewing"
+        if _dot3(PO, mp["normal"]) < 0.5 * float(dist):
             continue
         lvl = predict_scale(mp["max_distance"], dist, sf, L)
         rad = f32(f32(th) * f32(scale[lvl]))
@@ -902,18 +988,22 @@ def fuse(kps, desc, uright, bounds, scale, inv_sigma2, sf, cam, mps, mpdesc, th)
             if uright is not None and uright[idx] >= 0:
                 er = f32(ur - f32(uright[idx]))
                 e2 = f32(f32(f32(ex * ex) + f32(ey * ey)) + f32(er * er))
+                rec["chi2"].append((int(idx), f32(e2 * f32(inv_sigma2[o])), True))
                 return not float(f32(e2 * f32(inv_sigma2[o]))) > 7.8
             e2 = f32(f32(ex * ex) + f32(ey * ey))
+            rec["chi2"].append((int(idx), f32(e2 * f32(inv_sigma2[o])), False))
             return not float(f32(e2 * f32(inv_sigma2[o]))) > 5.99
-        best, bi = _kf_best(kps, desc, cells, bounds, u, v, rad, lvl, mpdesc[i], 256, reproj)
+        best, bi = _kf_best(kps, desc, cells, bounds, u, v, rad, lvl, mpdesc[i], 256, reproj, rec)
         if best <= 50:
             out[i] = bi
             nf += 1
     return np.array(out, np.int32), nf
 
 
-def fuse_sim3(kps, desc, bounds, scale, sf, cam, mps, mpdesc, th):
-    """Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (src/ORBmatcher.cc:977-1081), match part."""
+def fuse_sim3(kps, desc, bounds, scale, sf, cam, mps, mpdesc, th, trace=None):
+    """Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (src/ORBmatcher.cc:977-1081), match part.
+    trace: see _trace_recs."""
+    recs = _trace_recs(trace, len(mps))
     fx, fy, cx, cy, mb, mbf, S = _cam(cam)
     T = _sim3_T(S)
     cells = grid_cells(kps, bounds)
@@ -926,28 +1016,37 @@ def fuse_sim3(kps, desc, bounds, scale, sf, cam, mps, mpdesc, th):
         if not mp["valid"]:
             continue
         X, Y, Z = _mat_rx_t(T, mp["pos"])
+        rec = recs[i]
+        rec["stage"] = "depth"
         if Z < f32(0):
             continue
-        invz = f32(1.0 / float(Z))
-        u = f32(f32(fx * f32(X * invz)) + cx)
-        v = f32(f32(fy * f32(Y * invz)) + cy)
+        with np.errstate(divide="ignore", invalid="ignore"):  # z = 0: 1.0 / 0 = inf, 0 * inf = NaN
+            invz = f32(np.float64(1.0) / np.float64(Z))
+            u = f32(f32(fx * f32(X * invz)) + cx)
+            v = f32(f32(fy * f32(Y * invz)) + cy)
+        rec.update(stage="image", u=u, v=v)
         if not _in_image(u, v, bounds):
             continue
         PO = [f32(f32(mp["pos"][k]) - Ow[k]) for k in range(3)]
         dist = f32(_norm3(PO))
-        if not _dist_ok(mp, dist) or _dot3(PO, mp["normal"]) < 0.5 * float(dist):
+        rec.update(stage="distance", dist=dist)
+        if not _dist_ok(mp, dist):
+            continue
+        rec["stage"] = "viewing"
+        if _dot3(PO, mp["normal"]) < 0.5 * float(dist):
             continue
         lvl = predict_scale(mp["max_distance"], dist, sf, L)
         rad = f32(f32(th) * f32(scale[lvl]))
-        best, bi = _kf_best(kps, desc, cells, bounds, u, v, rad, lvl, mpdesc[i], 1 << 31)
+        best, bi = _kf_best(kps, desc, cells, bounds, u, v, rad, lvl, mpdesc[i], 1 << 31, None, rec)
         if best <= 50:
             out[i] = bi
             nf += 1
     return np.array(out, np.int32), nf
 
 
-def search_by_sim3(kf1, kf2, cam1, s12, R12, t12, th, sf=1.2):
-    """SearchBySim3 (src/ORBmatcher.cc:1102-1326)."""
+def search_by_sim3(kf1, kf2, cam1, s12, R12, t12, th, sf=1.2, trace=None):
+    """SearchBySim3 (src/ORBmatcher.cc:1102-1326). trace: receives two lists of records (see
+    _trace_recs), direction 1 (pKF1's points in pKF2) and direction 2."""
     fx, fy, cx, cy = f32(cam1.fx), f32(cam1.fy), f32(cam1.cx), f32(cam1.cy)
     R = np.asarray(R12, np.float32).reshape(3, 3)
     t = np.asarray(t12, np.float32).reshape(3)
@@ -967,25 +1066,34 @@ def search_by_sim3(kf1, kf2, cam1, s12, R12, t12, th, sf=1.2):
         cells = grid_cells(B["kps"], B["bounds"])
         L = len(B["scale"])
         vm = [-1] * len(A["kps"])
+        recs = _trace_recs(None, len(A["kps"]))
+        if trace is not None:
+            trace.append(recs)
         for i in range(len(A["kps"])):
             mp = A["mps"][i]
             if not mp["valid"]:
                 continue
             p1 = _mat_rx_t(np.asarray(A["Tcw"], np.float32), mp["pos"])
             p2 = _mat_rx_t(S, p1)
+            rec = recs[i]
+            rec["stage"] = "depth"
             if p2[2] < 0.0:
                 continue
-            invz = f32(1.0 / float(p2[2]))
-            u = f32(f32(fx * f32(p2[0] * invz)) + cx)
-            v = f32(f32(fy * f32(p2[1] * invz)) + cy)
+            with np.errstate(divide="ignore", invalid="ignore"):  # z = 0: 1.0 / 0 = inf, 0 * inf = NaN
+                invz = f32(np.float64(1.0) / np.float64(p2[2]))
+                u = f32(f32(fx * f32(p2[0] * invz)) + cx)
+                v = f32(f32(fy * f32(p2[1] * invz)) + cy)
+            rec.update(stage="image", u=u, v=v)
             if not _in_image(u, v, B["bounds"]):
                 continue
             dist = f32(_norm3(p2))
+            rec.update(stage="distance", dist=dist)
             if not _dist_ok(mp, dist):
                 continue
             lvl = predict_scale(mp["max_distance"], dist, sf, L)
             rad = f32(f32(th) * f32(B["scale"][lvl]))
-            best, bi = _kf_best(B["kps"], B["desc"], cells, B["bounds"], u, v, rad, lvl, A["mpdesc"][i], 1 << 31)
+            best, bi = _kf_best(B["kps"], B["desc"], cells, B["bounds"], u, v, rad, lvl, A["mpdesc"][i], 1 << 31,
+                                None, rec, 100)
             if best <= 100:
                 vm[i] = bi
         return vm
